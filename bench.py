@@ -6,12 +6,18 @@ finalize/compaction + result copy back to the host), i.e. one `lk_eval_pushdown`
 call.  Weak scaling: every GPU holds `--segments` segments of `--rows` rows (C2: 64 x 2^24); at N > 1 the
 request names all N x 64 segments, each rank scans its shard and the partial tables meet on rank 0 over RCCL.
 
-    python bench.py                      # N=1, C2
+    python bench.py                      # N=1, C2: set up, warm up, time the steps, print the result line
+    python bench.py --full               # ... and everything else the bench measures and checks (below)
+    python bench.py --dump-outputs DIR   # ... and write the last timed step's rows as DIR/<name>.npy
     python bench.py --gpus 8             # N=8: this process starts the 8 rank processes itself (one per GPU)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8
     python bench.py --gpus 2 --comm host # rehearsal: 2 ranks on one GPU over the host transport
 
-At N > 1 every rank times the CPU restatement on its own shard and sends its partial cells to rank 0, which folds
+A plain run does only what the headline figure (`value`, `ms_per_step`) needs.  `--full` adds the untimed
+plan-bytes pass and the roofline figures, the cold evaluation, the stream-copy rate, the CPU baseline with the
+full-size validation against it, and the attached PMC traffic summary.
+
+With --full at N > 1 every rank times the CPU restatement on its own shard and sends its partial cells to rank 0, which folds
 them with query-api semantics and checks the merged GPU rows against them (`validated`); `cpu_baseline` is the
 whole workload's rows over the slowest rank's shard time.
 """
@@ -182,8 +188,15 @@ def main():
     ap.add_argument("--query", default=None, choices=sorted(QUERIES),
                     help="default: c2 (BASELINE configs[1]) at N=1, c4 (configs[3]: :sum :by service, 64 segments "
                          "per GPU) at N > 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: plan bytes and roofline, cold "
+                         "evaluation, stream-copy rate, CPU baseline and full-size validation, PMC traffic summary")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the rows the last timed step returned as DIR/<name>.npy "
+                         "(float64: timestamps, values, globs, tag_hash)")
     ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="segments per rank timed on the CPU restatement (-1: all = full-size validation; 0: skip)")
+                    help="with --full: segments per rank timed on the CPU restatement (-1: all = full-size "
+                         "validation; 0: skip)")
     ap.add_argument("--gen-workers", type=int, default=4)
     ap.add_argument("--comm", default="rccl", choices=["rccl", "host"],
                     help="N > 1 exchange: RCCL over xGMI (default), or the host transport over gloo (rehearsal of the "
@@ -252,7 +265,7 @@ def main():
                                                         ts_shuffle=q.get("ts_shuffle", 0)))
 
     # The CPU baseline / validator reads the same Parquet bytes: every rank keeps its shard in host memory.
-    keep_cpu = args.cpu_sample != 0
+    keep_cpu = args.full and args.cpu_sample != 0
     kept = {}
     t0 = time.time()
     bytes_loaded = 0
@@ -292,24 +305,29 @@ def main():
 
     # Plan bytes (the roofline numerator) are a property of the query and the data: counted by the kernel in one
     # untimed call (LK_PLAN_BYTES costs ~5% of scan time), then the timed steps run without the counter.  Per GPU:
-    # this rank's shard alone (the same scan work it does inside the distributed call).
-    pbytes = float(eng.eval_pushdown(local_req, [keys[i] for i in mine], 10, LK_MERGED | LK_PLAN_BYTES)
-                   .stats.get("plan_bytes", 0))
+    # this rank's shard alone (the same scan work it does inside the distributed call).  --full only.
+    pbytes = None
+    if args.full:
+        pbytes = float(eng.eval_pushdown(local_req, [keys[i] for i in mine], 10, LK_MERGED | LK_PLAN_BYTES)
+                       .stats.get("plan_bytes", 0))
     for _ in range(args.warmup):
         res = step()
-    # Cold evaluation: the request as if never seen -- parse, leaf-outcome, value-key-order and group-dim caches
-    # dropped (segments stay resident) -- one call, wall time; then one warm call so the timed steps start warm.
-    if world > 1:
-        dist.barrier()
-    eng.drop_caches()
-    tc = time.perf_counter()
-    cold = step()
-    cold_ms = (time.perf_counter() - tc) * 1e3
-    cold_total_ms = cold.stats.get("total_ms")
-    cold_stages = {k: cold.stats.get(k) for k in ("plan_ms", "dims_ms", "dims_rebuilt", "scan_ms", "device_ms",
-                                                   "reduce_ms", "scan_agreed_ms") if k in cold.stats}
-    del cold
-    res = step()
+    # Cold evaluation (--full only): the request as if never seen -- parse, leaf-outcome, value-key-order and
+    # group-dim caches dropped (segments stay resident) -- one call, wall time; then one warm call so the timed
+    # steps start warm.
+    cold_ms = None
+    if args.full:
+        if world > 1:
+            dist.barrier()
+        eng.drop_caches()
+        tc = time.perf_counter()
+        cold = step()
+        cold_ms = (time.perf_counter() - tc) * 1e3
+        cold_total_ms = cold.stats.get("total_ms")
+        cold_stages = {k: cold.stats.get(k) for k in ("plan_ms", "dims_ms", "dims_rebuilt", "scan_ms", "device_ms",
+                                                       "reduce_ms", "scan_agreed_ms") if k in cold.stats}
+        del cold
+        res = step()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -356,21 +374,26 @@ def main():
     rows_total = total * args.rows
     value = rows_total / (ms_per_step / 1e3)
     scan_avg = avg(scan_ms)
-    # Roofline numerator: the bytes the late-materialized plan must read, counted by the scan kernel (streams it
-    # decodes in full + distinct 128-B lines of its per-row gathers + tile metadata), per launch.
-    achieved = pbytes / (scan_avg / 1e3) / 1e9
+    # Roofline numerator (--full): the bytes the late-materialized plan must read, counted by the scan kernel
+    # (streams it decodes in full + distinct 128-B lines of its per-row gathers + tile metadata), per launch.
+    achieved = pbytes / (scan_avg / 1e3) / 1e9 if args.full else None
     alg_gbs = alg_bytes / (scan_avg / 1e3) / 1e9
-    log(f"rank {rank}: scan kernel {scan_avg:.3f} ms avg (min {min(scan_ms):.3f}), eval {ms_per_step:.3f} ms/step, "
-        f"plan bytes {pbytes / 1e9:.2f} GB/launch -> {achieved:.0f} GB/s ({achieved / HBM_PEAK_GBS:.3f} of peak); "
+    log(f"rank {rank}: scan kernel {scan_avg:.3f} ms avg (min {min(scan_ms):.3f}), eval {ms_per_step:.3f} ms/step, " +
+        (f"plan bytes {pbytes / 1e9:.2f} GB/launch -> {achieved:.0f} GB/s ({achieved / HBM_PEAK_GBS:.3f} of peak); "
+         if args.full else "") +
         f"SURVEY algorithmic {alg_bytes / 1e9:.2f} GB -> {alg_gbs:.0f} GB/s; {out_rows} output rows; in the call: "
         f"plan {avg(plan_ms):.2f} ms, device {avg(device_ms):.2f} ms, total {avg(total_ms):.2f} ms" +
         (f"; group-dim agreement {avg(dims_ms):.2f} ms, reduce {res.stats.get('reduce')}, "
          f"emit {res.stats.get('emit')}, reduce stage {avg(reduce_ms):.3f} ms, "
-         f"collectives {res.stats.get('collectives')}" if use_dist else "") + f"; cold eval {cold_ms:.2f} ms")
+         f"collectives {res.stats.get('collectives')}" if use_dist else "") +
+        (f"; cold eval {cold_ms:.2f} ms" if args.full else ""))
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     # measured device-to-device copy rate on this GPU (a stream-copy peak beside the spec peak)
     copy_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         a = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
         b = torch.empty_like(a)
         b.copy_(a)
@@ -396,9 +419,10 @@ def main():
     # Accepted only when that summary was taken with this very library build (sha256 of the loaded .so) and counted
     # the same plan bytes: a PMC pass of an older kernel says nothing about this one, so otherwise traffic is null.
     traffic, traffic_src = None, None
-    lib_sha = _lib_sha16()
+    lib_sha = _lib_sha16() if args.full else None
     pmc_file = None
-    for rnd in ("r06", "r05", "r04", "r03", "r02"):   # the newest committed PMC summary of this query
+    rounds = ("r06", "r05", "r04", "r03", "r02") if args.full else ()
+    for rnd in rounds:   # the newest committed PMC summary of this query
         cand = os.path.join(ROOT, "profiles", f"{rnd}_pmc_{args.query}.json")
         if os.path.exists(cand):
             pmc_file = cand
@@ -433,40 +457,43 @@ def main():
                      "gbs": bytes_loaded / load_s / 1e9 if load_s else None,
                      "ms_per_segment": load_s / S * 1e3},
             "rows_scanned": rows_total, "output_rows": out_rows,
-            "scan_kernel_ms": scan_avg, "eval_ms": ms_per_step,
-            "cold_eval_ms": cold_ms,
-            "cold_eval": {"what": "first evaluation of the request after lk_engine_drop_caches (parsed request, "
-                                  "leaf outcomes, value-key orders, group-dim unions dropped; segments resident); "
-                                  "wall time of the call", "ms": cold_ms, "engine_total_ms": cold_total_ms,
-                          "stages": cold_stages},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "definition": "achieved = plan bytes per launch (counted by the scan kernel: streams "
-                                       "decoded in full + distinct 128-B lines of every per-row gather + tile "
-                                       "metadata) / scan-kernel time (HIP events on the call's stream), rank 0's "
-                                       "shard at N > 1. `value` "
-                                       "counts every row of the workload as scanned, including rows of tiles whose "
-                                       "load-time zone map (timestamp min/max per tile) pins them to a single "
-                                       "bucket and of split tiles (timestamps never decreasing: the bucket "
-                                       "boundary rows are found by searching them, r05): their timestamps are "
-                                       "never gathered per row, and value lines with no passing row are skipped, "
-                                       "so plan bytes < SURVEY's algorithmic bytes; a plan change that reads fewer "
-                                       "bytes lowers `frac` at equal time -- compare `value` and scan time across "
-                                       "rounds",
-                         "plan_bytes_per_launch": pbytes,
-                         "algorithmic_bytes_per_launch": alg_bytes, "algorithmic_gbs": alg_gbs,
-                         "frac_algorithmic": alg_gbs / HBM_PEAK_GBS,
-                         "frac_algorithmic_note": "SURVEY §8(d)'s algorithmic bytes (every referenced column chunk in "
-                                                  "full) / scan-kernel time / 8 TB/s, beside `frac` (plan bytes): above "
-                                                  "1 when the plan skips bytes §8(d) counts (zone-mapped / split-tile "
-                                                  "timestamps, value lines with no passing row)",
-                         "traffic_source": traffic_src,
-                         "traffic_gbs": traffic / (scan_avg / 1e3) / 1e9 if traffic else None,
-                         "stream_copy_gbs": copy_gbs},
-            "validated": validated,
-            "lib_sha16": lib_sha,
-            "cpu_baseline": cpu,
+            "scan_kernel_ms": scan_avg, "eval_ms": ms_per_step, "full": args.full,
         }
+        if args.full:   # what the --full legs measured and checked
+            line.update({
+                "cold_eval_ms": cold_ms,
+                "cold_eval": {"what": "first evaluation of the request after lk_engine_drop_caches (parsed request, "
+                                      "leaf outcomes, value-key orders, group-dim unions dropped; segments resident); "
+                                      "wall time of the call", "ms": cold_ms, "engine_total_ms": cold_total_ms,
+                              "stages": cold_stages},
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                             "definition": "achieved = plan bytes per launch (counted by the scan kernel: streams "
+                                           "decoded in full + distinct 128-B lines of every per-row gather + tile "
+                                           "metadata) / scan-kernel time (HIP events on the call's stream), rank 0's "
+                                           "shard at N > 1. `value` "
+                                           "counts every row of the workload as scanned, including rows of tiles whose "
+                                           "load-time zone map (timestamp min/max per tile) pins them to a single "
+                                           "bucket and of split tiles (timestamps never decreasing: the bucket "
+                                           "boundary rows are found by searching them, r05): their timestamps are "
+                                           "never gathered per row, and value lines with no passing row are skipped, "
+                                           "so plan bytes < SURVEY's algorithmic bytes; a plan change that reads fewer "
+                                           "bytes lowers `frac` at equal time -- compare `value` and scan time across "
+                                           "rounds",
+                             "plan_bytes_per_launch": pbytes,
+                             "algorithmic_bytes_per_launch": alg_bytes, "algorithmic_gbs": alg_gbs,
+                             "frac_algorithmic": alg_gbs / HBM_PEAK_GBS,
+                             "frac_algorithmic_note": "SURVEY §8(d)'s algorithmic bytes (every referenced column chunk in "
+                                                      "full) / scan-kernel time / 8 TB/s, beside `frac` (plan bytes): above "
+                                                      "1 when the plan skips bytes §8(d) counts (zone-mapped / split-tile "
+                                                      "timestamps, value lines with no passing row)",
+                             "traffic_source": traffic_src,
+                             "traffic_gbs": traffic / (scan_avg / 1e3) / 1e9 if traffic else None,
+                             "stream_copy_gbs": copy_gbs},
+                "validated": validated,
+                "lib_sha16": lib_sha,
+                "cpu_baseline": cpu,
+            })
         if use_dist:   # the distributed call's own stages (rank 0): group-dim agreement, table reduce, row emission
             line["comm_world"] = (comm_desc or {}).get("world")
             line["dist"] = {"dims_ms": avg(dims_ms), "reduce": res.stats.get("reduce"),
@@ -486,6 +513,33 @@ def main():
     if world > 1:
         dist.destroy_process_group()
     eng.close()
+
+
+DUMP_MAX_ROWS = 1 << 20   # 4 float64 arrays of this many rows = 32 MiB
+
+
+def dump_outputs(out_dir, res):
+    """Write the rows of one evaluation -- what the caller of the timed step receives -- as float64 .npy files under
+    `out_dir`, in row order: timestamps (epoch ms, exact in a double), values, globs, and tag_hash (48 bits of blake2b
+    over the row's sorted tag map, so two builds can be compared row for row without the strings).  A result of
+    more than DUMP_MAX_ROWS rows is sampled at row indices drawn once from a fixed seed (sorted; the same rows for
+    the same row count); row_index.npy then holds them."""
+    import hashlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(res)
+    idx = None
+    if n > DUMP_MAX_ROWS:
+        idx = np.sort(np.random.default_rng(20240101).choice(n, DUMP_MAX_ROWS, replace=False))
+        np.save(os.path.join(out_dir, "row_index.npy"), idx.astype(np.float64))
+    for name, col in (("timestamps", res.ts), ("values", res.values), ("globs", res.globs)):
+        np.save(os.path.join(out_dir, name + ".npy"), (col if idx is None else col[idx]).astype(np.float64))
+    tags = res.tags
+    rows = range(n) if idx is None else idx.tolist()
+    th = [int.from_bytes(hashlib.blake2b(json.dumps(sorted(tags[r].items())).encode(), digest_size=6).digest(), "big")
+          for r in rows]
+    np.save(os.path.join(out_dir, "tag_hash.npy"), np.array(th, dtype=np.float64))
+    log(f"wrote {n if idx is None else len(idx)} of {n} output rows to {out_dir}")
 
 
 def _lib_sha16():

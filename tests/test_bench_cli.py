@@ -1,5 +1,5 @@
-"""bench.py's launcher contract, on the CPU (no GPU here): `--gpus N` without an external launcher starts N rank
-processes itself, and refuses -- loudly, with a non-zero status -- when the GPUs it needs are not visible, instead of
+"""bench.py's launcher contract, on the CPU (any GPU of this host is hidden from the bench): `--gpus N` without an
+external launcher starts N rank processes itself, and refuses -- loudly, with a non-zero status -- when the GPUs it needs are not visible, instead of
 degrading to one process."""
 import os
 import subprocess
@@ -10,6 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _run(args, env_extra=None):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"   # these tests are about a host that shows no GPU: hide any this one has
     env.update(env_extra or {})
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True,
                           timeout=600, env=env, cwd=ROOT)
