@@ -169,6 +169,7 @@ int lk_engine_drop_caches(lk_engine* e) {
   {
     std::lock_guard<std::mutex> g(E.leaf_mu);
     E.leaf_cache.clear();
+    E.field_tabs.clear();
   }
   {
     std::lock_guard<std::mutex> g(E.order_mu);

@@ -422,6 +422,7 @@ void Engine::compact_locked(const std::string& col) {
     const std::string pre = col + '\x1f';
     for (auto it = leaf_cache.begin(); it != leaf_cache.end();)
       it = it->first.compare(0, pre.size(), pre) == 0 ? leaf_cache.erase(it) : std::next(it);
+    field_tabs.erase(col);
   }
   {
     std::lock_guard<std::mutex> g(order_mu);
@@ -705,6 +706,13 @@ void Engine::release_ctx(std::unique_ptr<CallCtx> c) {
     ctx_free.push_back(std::move(c));
   }
   ctx_cv.notify_one();
+}
+
+std::shared_ptr<FieldTab> Engine::field_tab(const std::string& col) {
+  std::lock_guard<std::mutex> g(leaf_mu);
+  auto& slot = field_tabs[col];
+  if (!slot) slot = std::make_shared<FieldTab>();
+  return slot;
 }
 
 std::shared_ptr<LeafBits> Engine::leaf_bits(const std::string& key) {

@@ -34,6 +34,10 @@ struct Segment : SegmentData {
   bool from_put = false;                         // registered by lk_segment_put (its key is not a file path)
   std::atomic<uint64_t> last_use{0};             // LRU clock value of the last lookup (cache eviction)
   struct Engine* engine = nullptr;               // whose dictionaries its remaps reference (refs released at ~Segment)
+  // field charts over a VARCHAR column of this segment (by column index): every value it references is a number or
+  // casts to NULL (FieldTab) -- a property of the file, kept across queries and dictionary compactions
+  mutable std::mutex field_mu;
+  mutable std::map<int, bool> field_text_ok;
   ~Segment();
 };
 
@@ -122,6 +126,15 @@ struct LeafBits {
   std::vector<uint8_t> hit;   // one byte per evaluated dictionary value
 };
 
+// Field charts over a VARCHAR field (chart.fieldName, eval.cpp): per value of the column's engine dictionary the double
+// `try_cast(.. as double)` gives (lk_field_number, fieldnum.cpp).  cls: 1 a number (val), 0 NULL, -1 text this engine
+// does not answer.  Extended as the dictionary grows, so a value is parsed once.
+struct FieldTab {
+  std::mutex mu;
+  std::vector<double> val;
+  std::vector<int8_t> cls;
+};
+
 struct Engine {
   int device = 0;
   size_t max_calls = 4;                          // evaluation contexts (streams) in flight
@@ -174,6 +187,8 @@ struct Engine {
   std::mutex leaf_mu;
   std::map<std::string, std::shared_ptr<LeafBits>> leaf_cache;   // key: column \x1f op \x1f values
   std::shared_ptr<LeafBits> leaf_bits(const std::string& key);
+  std::map<std::string, std::shared_ptr<FieldTab>> field_tabs;   // per column (under leaf_mu); dropped by a compaction
+  std::shared_ptr<FieldTab> field_tab(const std::string& col);
   Comm* comm = nullptr;                          // set once by lk_comm_init* (under comm_init_mu), never replaced
   std::mutex comm_init_mu;                       //   guards the set-once check and comm_desc
   std::string comm_desc = "null";                //   comm->describe() taken at init: lk_engine_stats reads this copy

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/lakeside_gpu.h"
+#include "../../include/lakeside_text.h"
 #include "comm.hpp"
 #include "engine.hpp"
 #include "kernels.hpp"
@@ -302,6 +303,79 @@ void expand_rows_from_keys(Engine& E, int64_t* ts, uint32_t* gid, uint32_t* glob
 }
 }  // namespace
 
+namespace {
+// The column's FieldTab over dictionary ids [0, n) (values below n are immutable; the caller holds ft.mu).
+void extend_field_tab(FieldTab& ft, const GlobalDict& gd, uint32_t n) {
+  ft.val.reserve(n);
+  ft.cls.reserve(n);
+  for (uint32_t id = uint32_t(ft.cls.size()); id < n; id++) {
+    const std::string& s = gd[id];
+    double v = 0.0;
+    const int c = lk_field_number(s.data(), s.size(), &v);
+    ft.val.push_back(c == 1 ? v : 0.0);
+    ft.cls.push_back(int8_t(c));
+  }
+}
+
+// A field chart over VARCHAR column `c` of segment S: every value the column's chunk dictionaries reference must be a
+// number or cast to NULL (FieldTab::cls); *bad names the first one that is neither.  The ids come from the segment's
+// device remap (the host copy is dropped after the upload); the verdict is kept with the segment.
+bool segment_text_ok(Engine& E, const Segment& S, int c, const FieldTab& ft, std::string* bad) {
+  std::lock_guard<std::mutex> g(S.field_mu);
+  auto it = S.field_text_ok.find(c);
+  if (it != S.field_text_ok.end() && it->second) return true;   // (a refused column is searched again for its message)
+  const HostCol& hc = S.cols[size_t(c)];
+  std::vector<uint32_t> ids(hc.nremap);
+  if (hc.nremap) {
+    HIP_TRY(hipSetDevice(E.device));
+    HIP_TRY(hipMemcpy(ids.data(), hc.d_remap, hc.nremap * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  const GlobalDict& gd = E.dict(hc.name);
+  bool ok = true;
+  for (uint32_t id : ids) {
+    if (id >= ft.cls.size()) throw PlanError(LK_ERR_DEVICE, "internal: dictionary id beyond the field table");
+    if (ft.cls[id] >= 0) continue;
+    ok = false;
+    *bad = gd[id];
+    break;
+  }
+  S.field_text_ok[c] = ok;
+  return ok;
+}
+}  // namespace
+
+// Field charts (chart.fieldName / fieldType).  For logs and traces with a standard aggregate BaseExpr.getChartSql
+// (BaseExpr.scala:319-405) emits
+//   SELECT <step_ts>, <agg>(try_cast(<fieldName>$<fieldType> as double)) [/ 1000000 | / 1000], "_cardinalhq.name" as name ..
+//   FROM (..) WHERE <fieldName>$<fieldType> IS NOT NULL AND <filter> GROUP BY ..
+// -- the value chart's scan over another column, one more conjunct and a constant divisor (duration: nanoseconds to
+// ms, datasize: to KB, BaseExpr.scala:363-367).  The shapes evaluated are the ones whose SQL this engine can restate
+// without guessing what DuckDB binds; every other one fails with LK_ERR_UNSUPPORTED and a message naming its rule
+// (field charts).  Returns the divisor (0.0: none); every rule depends on the request alone.
+static double field_chart_gate(const Request& R, int agg, bool per_glob_rows) {
+  auto refuse = [](const std::string& why) -> double { throw PlanError(LK_ERR_UNSUPPORTED, "field chart: " + why); };
+  if (R.dataset != "logs" && R.dataset != "traces") refuse("the dataset must be logs or traces, not " + R.dataset);
+  if (agg != AGG_SUM && agg != AGG_MIN && agg != AGG_MAX && agg != AGG_COUNT && agg != AGG_AVG)
+    refuse("aggregation " + R.aggregation + (R.rollup.empty() ? "" : " (rollup " + R.rollup + ")") +
+           "; sum, min, max, count and avg are evaluated");
+  if (!R.field_type) return 0.0;   // generateSql throws (BaseExpr.scala:355-356): every glob is empty (evaluate_once)
+  // the column is written unquoted (BaseExpr.scala:357-362): only names an unquoted DuckDB identifier keeps as they are
+  const std::string col = value_column(R);
+  bool plain = !col.empty() && !(col[0] >= '0' && col[0] <= '9') && col[0] != '$';
+  for (char c : col) plain = plain && ((c >= 'a' && c <= 'z') || (c >= '0' && c <= '9') || c == '_' || c == '$');
+  if (!plain) refuse("column " + col + " is not of the form [a-z_][a-z0-9_$]*");
+  // Commons.toDataPoint resets the value to a result tag named fieldName (Commons.scala:442-447)
+  if (std::find(R.group_bys.begin(), R.group_bys.end(), *R.field_name) != R.group_bys.end())
+    refuse("fieldName " + *R.field_name + " is also a groupBy (resetValueToField)");
+  const double scale = *R.field_type == "duration" ? 1e6 : (*R.field_type == "datasize" ? 1e3 : 0.0);
+  if (scale != 0.0) {
+    // COUNT(..) / 1000 divides a BIGINT by an integer literal: integer or float division by DuckDB version
+    if (agg == AGG_COUNT) refuse("count over a " + *R.field_type + " field");
+    if (agg == AGG_AVG && !per_glob_rows) refuse("merged avg over a " + *R.field_type + " field (its SUM / COUNT split)");
+  }
+  return scale;
+}
+
 static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, const char* const* paths, size_t n_paths,
                          int glob_size, unsigned flags, const int32_t* shard, bool dist, lk_result* res, unsigned redo);
 // internal evaluation flag: per-glob rows of a distributed call (rank 0 receives them), for evaluate_metrics_pct
@@ -353,7 +427,7 @@ int evaluate(Engine& E, const std::string& json, const char* const* paths, size_
              unsigned flags, const int32_t* shard, bool dist, lk_result* res) {
   const std::shared_ptr<const Request> Rp = E.parse_cached(json);
   if (Rp->dataset == "metrics" && Rp->has_chart && !Rp->is_tag_query && Rp->aggregation.size() > 1 &&
-      Rp->aggregation[0] == 'p' && !Rp->field_chart && !Rp->has_extract && !Rp->has_compute)
+      Rp->aggregation[0] == 'p' && !Rp->field_chart() && !Rp->has_extract && !Rp->has_compute)
     return evaluate_metrics_pct(E, json, *Rp, paths, n_paths, glob_size, flags, shard, dist, res);
   if (n_paths == Rp->segments.size() && mixed_steps(*Rp, glob_size <= 0 ? 10 : glob_size))
     return evaluate_mixed_steps(E, json, *Rp, paths, n_paths, glob_size <= 0 ? 10 : glob_size, flags, shard, dist, res);
@@ -636,8 +710,9 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   // the worker's SQL: the tag column's own type decides; a numeric tag column takes the row scan, below)
   if (!tagq && R.is_tag_query)   // isTagQuery without a tagDataType: SELECT * ... WHERE <filter> (BaseExpr.scala:231-232)
     throw PlanError(LK_ERR_UNSUPPORTED, "tag queries without a tagDataType");
-  if (R.field_chart || R.has_extract || R.has_compute)
-    throw PlanError(LK_ERR_UNSUPPORTED, "extract / compute / field charts are not on the hot path");
+  if (R.has_extract || R.has_compute) throw PlanError(LK_ERR_UNSUPPORTED, "extract / compute are not on the hot path");
+  const bool fchart = R.field_chart();
+  if (fchart && R.is_tag_query) throw PlanError(LK_ERR_UNSUPPORTED, "field chart: a tag query takes no chart field");
   if (R.dataset != "logs" && R.dataset != "traces" && R.dataset != "metrics")
     throw PlanError(LK_ERR_ARG, "Invalid dataset: " + R.dataset);
   int agg;
@@ -664,6 +739,8 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   const bool ces = agg == AGG_CES;
   // queries whose SQL references no value column: tag queries (COUNT(*)) and metrics `ces` (1.0 per row)
   const bool no_value_col = tagq || (ces && R.dataset == "metrics");
+  // Field chart (chart.fieldName / fieldType): the same scan over `<fieldName>$<fieldType>` (field_chart_gate)
+  const double fscale = fchart ? field_chart_gate(R, agg, per_glob_rows) : 0.0;
   double quantile = 0.0;
   if (sketch) {
     char* end = nullptr;
@@ -711,6 +788,14 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
       res->gid[0] = 0;
     }
     res->stats = "{\"scan_ms\":0,\"total_ms\":0,\"rows_scanned\":0,\"algorithmic_bytes\":0,\"tiles\":0,\"cells\":0}";
+    return LK_OK;
+  }
+  // fieldName without fieldType: generateSql throws inside toGlobResultSet's try (BaseExpr.scala:355-356,
+  // Commons.scala:228-253), so every glob is empty and the call succeeds -- no segment is read (every rank alike)
+  if (fchart && !R.field_type) {
+    res->per_glob = per_glob_rows;
+    res->stats = "{\"scan_ms\":0,\"total_ms\":0,\"rows_scanned\":0,\"algorithmic_bytes\":0,\"tiles\":0,\"cells\":0,"
+                 "\"segments\":0,\"general_segments\":0,\"field_chart\":\"no fieldType\"}";
     return LK_OK;
   }
 
@@ -859,10 +944,17 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   // be NULL".  Layout: [globs x np exists | globs fail | globs value-type rank | value NULLs].
   const size_t np = probe_cols.size();
   const size_t ng = globs.size();
-  // [.. | value NULLs | numeric tag column]
-  std::vector<uint8_t> exists(ng * np + 2 * ng + 2, 0);
+  // [.. | value NULLs | numeric tag column | globs: a numeric file of the chart field | globs: a VARCHAR file of it]
+  std::vector<uint8_t> exists(ng * np + 2 * ng + 2 + 2 * ng, 0);
   const size_t vnull_at = ng * np + 2 * ng;
   exists[vnull_at + 1] = tag_numeric ? 1 : 0;
+  uint8_t* gfnum = exists.data() + vnull_at + 2;
+  uint8_t* gftext = gfnum + ng;
+  // Field chart over a VARCHAR field: the column's dictionary as doubles (FieldTab), extended to the dictionary's size
+  // now -- every segment of this call is loaded, so its ids lie below it
+  std::shared_ptr<FieldTab> ftab;
+  std::unique_lock<std::mutex> ftab_guard;
+  uint32_t ftab_n = 0;
   // A referenced column this engine does not decode (Segment::unloaded) fails the call with LK_ERR_UNSUPPORTED: DuckDB
   // would read it, so the shim must fall back rather than see an empty glob.  Rank-local (it depends on
   // this rank's segments): agreed on with the load status below.
@@ -904,7 +996,47 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
         return value_rank(hc.ptype) == 0;   // value column / numeric comparison column
       };
       if (bad(kTimestamp, 0)) gfail[gi] = 1;
-      if (!no_value_col) {
+      if (fchart) {
+        // The chart field per file: numeric (unified over the glob as the value column is) or VARCHAR (try_cast of
+        // its text); BOOLEAN -- and a VARCHAR value this engine does not cast -- fail the call, never a glob alone.
+        // Rank-local: agreed on with the load status below.
+        auto fail_call = [&](const std::string& m) {
+          if (load_err) return;
+          if (!dist) throw PlanError(LK_ERR_UNSUPPORTED, m);
+          load_err = LK_ERR_UNSUPPORTED;
+          load_msg = m;
+        };
+        if (vc >= 0 && S.cols[size_t(vc)].is_string) {
+          gftext[gi] = 1;
+          exists[vnull_at] = 1;   // text that casts to NULL: a cell may hold no value
+          try {
+            if (!ftab) {
+              ftab = E.field_tab(vcol);
+              ftab_guard = std::unique_lock<std::mutex>(ftab->mu);
+              GlobalDict& gd = E.dict(vcol);
+              {
+                std::lock_guard<std::mutex> g(gd.mu);
+                ftab_n = uint32_t(gd.size());
+              }
+              extend_field_tab(*ftab, gd, ftab_n);
+            }
+            std::string badv;
+            if (!load_err && !segment_text_ok(E, S, vc, *ftab, &badv))
+              fail_call("field chart: " + vcol + " holds '" + json_escape(badv) + "', neither a plain number nor text that casts to NULL (" + S.key + ")");
+          } catch (const PlanError& e) {
+            if (!dist) throw;
+            if (!load_err) {
+              load_err = e.code;
+              load_msg = e.what();
+            }
+          }
+        } else if (vc >= 0 && value_rank(S.cols[size_t(vc)].ptype)) {
+          gfnum[gi] = 1;
+          gvrank[gi] = std::max<uint8_t>(gvrank[gi], uint8_t(value_rank(S.cols[size_t(vc)].ptype)));
+        } else if (S.all_columns.count(vcol)) {   // BOOLEAN (an unloaded physical type was refused above)
+          fail_call("field chart: column " + vcol + " is neither numeric nor VARCHAR (" + S.key + ")");
+        }
+      } else if (!no_value_col) {
         if (bad(vcol, 1)) {
           // sum / avg over a VARCHAR value column is DuckDB's Binder Error (empty glob); count / min / max over it
           // run in DuckDB and this engine does not implement them: the call fails (LK_ERR_UNSUPPORTED)
@@ -926,6 +1058,14 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   // every rank sees every glob's union, failures and value type; a rank-local engine failure fails every rank here
   if (dist) comm_agree_max_u8(E, *X, load_err, load_msg, exists.data(), exists.size());
   const bool value_nulls = exists[vnull_at] != 0;
+  bool ftext_any = false;   // field chart: some glob's chart field is VARCHAR
+  if (fchart)
+    for (size_t gi = 0; gi < ng; gi++) {
+      // union_by_name of a numeric and a VARCHAR file makes the column VARCHAR, the numbers printed as text: refused
+      if (gfnum[gi] && gftext[gi])
+        throw PlanError(LK_ERR_UNSUPPORTED, "field chart: column " + vcol + " is numeric in some files and VARCHAR in others of glob " + std::to_string(gi));
+      ftext_any = ftext_any || gftext[gi];
+    }
   if (exists[vnull_at + 1]) {   // agreed: a numeric tag column on some rank -- every rank takes the TAGNUM row scan
     segs.clear();
     return evaluate_exemplar(E, *X, R, paths, n_paths, glob_size, flags, true, res, R.tag_name, shard);
@@ -1307,7 +1447,9 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
       q.leaf_false = g.leaf_false;
       q.win_lo = g.win_lo;
       q.win_hi = g.win_hi;
-      bool general = numeric && !vleaf;
+      // (a field chart with a VARCHAR glob: every segment takes the row scan, whose `rows` count only rows with a
+      // field -- the fused kernels' `rows` count NULL fields too, and one table holds one meaning)
+      bool general = (numeric && !vleaf) || ftext_any;
       // (column types were checked per glob above: a type the query cannot bind emptied the glob)
       auto bind = [&](int qc, const std::string& name, bool want_string) {
         int c = S.col_index(name);
@@ -1326,6 +1468,7 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
           // an integer value column in a glob whose value type is FLOAT is cast to FLOAT first (DuckDB's implicit
           // BIGINT -> FLOAT of the union column), then aggregated as a float
           if (vunion == pq::FLOAT && hc.ptype != pq::FLOAT) pad |= VCONV_VIA_FLOAT;
+          if (hc.is_string) pad |= VCONV_TEXT;   // a field chart's VARCHAR field: the row scan reads FieldTab
           if (hc.int_abs_max < 0.0) vals_integral = false;
           vals_abs_max = std::max(vals_abs_max, hc.int_abs_max);
           vals_rows += double(S.num_rows);
@@ -1335,7 +1478,8 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
       };
       bind(0, kTimestamp, false);
       if (!q.cols[0].present) continue;            // no timestamps: every row fails the window
-      if (!no_value_col) bind(1, vcol, false);     // COUNT(*) / metrics `ces` read no value column
+      // COUNT(*) / metrics `ces` read no value column; a field chart's field may be VARCHAR (the whole glob then is)
+      if (!no_value_col) bind(1, vcol, fchart && gftext[gi] != 0);
       for (size_t s = 0; s < strs.size(); s++) bind(2 + dev_of[s], strs[s].name, true);
       for (size_t n = 0; n < nums.size(); n++) bind(int(2 + strs.size() + n), nums[n], false);
       // scan_lean takes every tile of this segment when no page of its three columns holds a NULL and every
@@ -1485,6 +1629,10 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
         flat.insert(flat.end(), fold_maps[s].begin(), fold_maps[s].end());
       }
   const size_t o_maps = reserve(flat.size() * 4);
+  // field chart over a VARCHAR field: per dictionary id the double and a validity bit (XParams::ftab / fok)
+  const bool ftext_tab = ftext_any && ftab;
+  const size_t o_fval = reserve(ftext_tab ? size_t(ftab_n) * 8 : 0);
+  const size_t o_fok = reserve(ftext_tab ? (size_t(ftab_n) + 31) / 32 * 4 : 0);
   const size_t stage_bytes = off;
   const size_t o_tail = reserve(64);   // host side only: the small-table epilogue's flags and row count (mapped)
   // host side only (mapped): the first row of every bucket, when a large result's timestamps are expanded on the host
@@ -1531,6 +1679,13 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   memset(hbuf + o_flags, 0, 16);
   if (!name_rank.empty()) memcpy(hbuf + o_rank, name_rank.data(), name_rank.size() * 4);
   if (!flat.empty()) memcpy(hbuf + o_maps, flat.data(), flat.size() * 4);
+  if (ftext_tab && ftab_n) {
+    memcpy(hbuf + o_fval, ftab->val.data(), size_t(ftab_n) * 8);
+    uint32_t* ok = reinterpret_cast<uint32_t*>(hbuf + o_fok);
+    memset(ok, 0, (size_t(ftab_n) + 31) / 32 * 4);
+    for (uint32_t id = 0; id < ftab_n; id++)
+      if (ftab->cls[id] == 1) ok[id >> 5] |= 1u << (id & 31u);
+  }
   const hipError_t up = hipMemcpyAsync(dbuf, hbuf, stage_bytes, hipMemcpyHostToDevice, st);
   if (up != hipSuccess) {
     (void)hipGetLastError();
@@ -1541,6 +1696,7 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
     }
   }
   }
+  if (ftab_guard.owns_lock()) ftab_guard.unlock();   // the table is staged: other calls may extend it
   P.segs = reinterpret_cast<const QSeg*>(dbuf + o_segs);
   P.flags = reinterpret_cast<uint32_t*>(dbuf + o_flags);
   P.truth = truth.empty() ? nullptr : reinterpret_cast<const uint32_t*>(dbuf + o_truth);
@@ -1652,6 +1808,10 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   const uint64_t out_keys = ncells == 0 ? 0 : (per_glob_rows ? ncells : (collapse ? nbuckets : nbuckets * ngroups));
   const bool fast_final = !dist && !hash_mode && !sketch && !ces && !rekey && ncells && out_keys <= (uint64_t(1) << 20) &&
                           !getenv("LK_NO_FAST_FINAL");
+  // field charts: `<field> IS NOT NULL` drops a row, so a cell exists iff a row with a field reached it.  The row
+  // scan applies the conjunct per row (rows != 0 says so); the fused kernels count every passing row, and a numeric
+  // field's rows with a field are its cnt -- a call with a VARCHAR glob runs on the row scan alone (above)
+  const uint32_t fexist = (fchart && !ftext_any) ? 1u : 0u;
   auto setup_final = [&](FParams& Fp, uint32_t fslots) {
     Fp.ngroups = ngroups;
     Fp.nbuckets = nbuckets;
@@ -1664,6 +1824,8 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
     Fp.bucket_base = bucket_base;
     Fp.step = P.step;
     Fp.nkeys = out_keys;
+    Fp.exist_cnt = fexist;
+    Fp.scale = fscale;
   };
   bool fast_done = false;         // rows already written by the speculative finalize
   uint32_t fast_rows = 0;
@@ -1749,6 +1911,11 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
       XG.agg = kagg;
       XG.hash = hash_mode ? 1 : 0;
       XG.q = P;
+      if (fchart) {   // `<field> IS NOT NULL` as a conjunct; a VARCHAR field's values from the staged table
+        XG.field = 1;
+        XG.ftab = ftext_tab ? reinterpret_cast<const double*>(dbuf + o_fval) : nullptr;
+        XG.fok = ftext_tab ? reinterpret_cast<const uint32_t*>(dbuf + o_fok) : nullptr;
+      }
       HIP_TRY(launch_ex_scan(XG, st));
     }
     HIP_TRY(hipEventRecord(X->ev_scan1, st));
@@ -1942,6 +2109,8 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
       Fk.name_stride = strs[0].stride ? strs[0].stride : 1;
       Fk.bucket_base = bucket_base;
       Fk.step = P.step;
+      Fk.exist_cnt = fexist;
+      Fk.scale = fscale;
       Fk.key_base = kb[size_t(rank)];
       Fk.cell_base = kb[size_t(rank)];
       Fk.nkeys = len;
@@ -2227,6 +2396,7 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
       RP.nbuckets = nbuckets;
       RP.ngroups = ngroups;
       RP.agg = kagg;
+      RP.exist_cnt = fexist;
       for (size_t s = 0; s < strs.size(); s++) {
         if (!strs[s].is_dim) continue;
         RP.stride[RP.ndims] = strs[s].stride;
@@ -2281,6 +2451,8 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
     S.name_rank = name_rank.empty() ? nullptr : reinterpret_cast<const uint32_t*>(dbuf + o_rank);
     S.bucket_base = bucket_base;
     S.step = P.step;
+    S.exist_cnt = fexist;
+    S.scale = fscale;
     const uint32_t nsb = sparse_blocks(cap);
     uint32_t* occ = static_cast<uint32_t*>(X->workspace("occ_counts", (size_t(nsb) + 2) * 4));
     HIP_TRY(launch_sparse_count(S, occ, st));

@@ -198,12 +198,16 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
   uint32_t carry[MAXQCOL];
 #pragma unroll
   for (int k = 0; k < MAXQCOL; k++) carry[k] = 0;
+  // field chart over a VARCHAR field: query column 1 holds dictionary codes
+  const bool vtext = aggm && X.field && (Sp->cols[1].pad & VCONV_TEXT);
 
   for (uint32_t c0 = 0; c0 < nrows; c0 += BLOCK) {
     const uint32_t r = c0 + uint32_t(tid);
     const bool inb = r < nrows;
     uint32_t T = 0, F = 0;
     bool ts_ok = false, v_ok = false, tag_ok = false;
+    bool v_def = false;   // the value column's definition level (field charts: a conjunct of the filter)
+    uint32_t fgl = 0;     // vtext: the global dictionary id of the row's text
     unsigned long long tag_raw = 0;
     int64_t ts = 0;
     double v = 0.0;
@@ -233,6 +237,16 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
         vi = h.vbase + carry[qc] + before + below;
         carry[qc] += all;
         ok = bit;
+      }
+      if (qc == 1 && vtext) {   // the code now; its double only once the row passes (no table access for dropped rows)
+        if (h.nruns == 0u) ok = false;   // no value in this tile: NULL
+        if (ok) {
+          const __amdgpu_buffer_rsrc_t rs = make_rsrc(h.vals, h.vals_len + 8);
+          const int ri = find_run(vr[1], int(h.nruns), vi);
+          fgl = h.remap[hybrid_get_buf(rs, vr[1][ri], vi, int(h.bw))];
+        }
+        v_def = ok;
+        continue;
       }
       if (qc < 2 || qc >= 2 + ns) {   // PLAIN numeric: timestamp, value, numeric filter column
         const bool w8 = h.kind == PAGE_PLAIN64;
@@ -269,6 +283,7 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
             v = (pad & VCONV_VIA_FLOAT) ? double(float(iv)) : double(iv);
           }
           v_ok = ok;
+          v_def = ok;
         } else {
           const uint32_t pt = Sp->cols[qc].pad;   // Parquet physical type of this segment's column
           const bool is_int = pt == 1u || pt == 2u;
@@ -326,6 +341,11 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
     }
     pass = pass && ts_ok && ts >= lo && ts < hi;
     if (X.mode == XMODE_AGG) {
+      if (X.field) pass = pass && v_def;   // `<field> IS NOT NULL`
+      if (pass && vtext) {
+        v = X.ftab[fgl];
+        v_ok = (X.fok[fgl >> 5] >> (fgl & 31u)) & 1u;
+      }
       if (pass) {
         const QParams& q = X.q;
         int64_t b;

@@ -40,6 +40,14 @@ struct OutRow {
   uint32_t glob;
 };
 
+// A cell exists when a row passed the filter; in a field chart over a numeric field (`<field> IS NOT NULL` is part of
+// the filter, FParams::exist_cnt) when it holds a value.
+__device__ __forceinline__ bool cell_live(const FParams& F, unsigned long long cell) {
+  return (F.exist_cnt ? F.cnt[cell] : F.rows[cell]) != 0;
+}
+// The finalized aggregate over the field chart's divisor: one IEEE division of the final double (FParams::scale).
+__device__ __forceinline__ double scaled(double v, double scale) { return scale != 0.0 ? v / scale : v; }
+
 __device__ __forceinline__ double cell_value(const FParams& F, unsigned long long cell) {
   unsigned long long cnt = F.cnt[cell];
   switch (F.agg) {
@@ -73,9 +81,9 @@ __device__ OutRow make_row(const FParams& F, unsigned long long key) {
     const unsigned long long g = key % F.ngroups, t = key / F.ngroups;
     const unsigned long long gs = t % F.nglob_slots, b = t / F.nglob_slots;
     const unsigned long long cell = (gs * F.nbuckets + b) * F.ngroups + g - F.cell_base;
-    if (F.rows[cell] == 0) return o;
+    if (!cell_live(F, cell)) return o;
     o.exists = true;
-    o.value = cell_value(F, cell);
+    o.value = scaled(cell_value(F, cell), F.scale);
     o.gid = g;
     o.glob = uint32_t(gs);
     return o;
@@ -89,7 +97,7 @@ __device__ OutRow make_row(const FParams& F, unsigned long long key) {
   for (uint32_t gs = 0; gs < F.nglob_slots; gs++) {
     for (unsigned long long g = g0; g < g0 + ng; g++) {
       unsigned long long cell = ((unsigned long long)gs * F.nbuckets + b) * F.ngroups + g - F.cell_base;
-      if (F.rows[cell] == 0) continue;
+      if (!cell_live(F, cell)) continue;
       unsigned long long c = F.cnt[cell];
       if (F.agg == AGG_SUM || F.agg == AGG_AVG) {
         double s, e;
@@ -117,6 +125,7 @@ __device__ OutRow make_row(const FParams& F, unsigned long long key) {
   else if (F.agg == AGG_COUNT) o.value = double(cnt);
   else if (F.agg == AGG_ROWS) o.value = double(nrows);
   else o.value = ext;
+  o.value = scaled(o.value, F.scale);
   return o;
 }
 
@@ -270,7 +279,7 @@ __global__ __launch_bounds__(256) void rekey_minmax(RParams R) {
   size_t i = size_t(blockIdx.x) * 256 + threadIdx.x;
   if (i >= R.ncells_in) return;
   unsigned long long rows = R.in_rows[i];
-  if (rows == 0) return;
+  if ((R.exist_cnt ? R.in_cnt[i] : rows) == 0) return;
   unsigned long long g = i % R.ngroups;
   unsigned long long b = (i / R.ngroups) % R.nbuckets;
   unsigned long long cg = 0;
@@ -296,7 +305,7 @@ constexpr int SB = 256;
 constexpr int SITEMS = 8;
 
 __device__ __forceinline__ bool slot_live(const SParams& S, unsigned long long i) {
-  return S.keys[i] != EMPTY && S.rows[i] != 0;
+  return S.keys[i] != EMPTY && (S.exist_cnt ? S.cnt[i] : S.rows[i]) != 0;
 }
 
 __global__ __launch_bounds__(SB) void sparse_count(SParams S, uint32_t* block_counts) {
@@ -436,6 +445,7 @@ __global__ __launch_bounds__(SB) void runs_write(SParams S, const unsigned long 
       else if (S.agg == AGG_AVG) value = S.per_glob ? (cnt ? (hi + lo) / double(cnt) : 0.0) : (hi + lo) / double(cnt);
       else if (S.rekey) value = order_dbl(oext);
       else value = ext;
+      if (S.scale != 0.0) value /= S.scale;   // field charts: one division of the final double
       const unsigned long long b = S.per_glob ? key / S.ngroups / S.nslots : (S.collapse ? key : key / S.ngroups);
       const uint32_t pos = off + wb + __popcll(m & ((1ull << lane) - 1ull));
       out_ts[pos] = S.bucket_base + (int64_t)b * S.step;

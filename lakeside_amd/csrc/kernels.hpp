@@ -37,6 +37,11 @@ struct FParams {
   // (mapped pinned memory), from which the host derives every row's timestamp, group id and glob -- finalize_write then
   // sends the values alone (8 of 20-24 bytes per row)
   unsigned long long* key_bits;
+  // field charts (chart.fieldName, BaseExpr.scala:355-367): `<field> IS NOT NULL` is a row filter, so a cell of a
+  // numeric field exists iff it holds a value (cnt != 0) rather than a passing row; the finalized value is divided by
+  // `scale` (duration: 1e6, datasize: 1e3) when it is non-zero.  0 / 0.0: value charts.
+  uint32_t exist_cnt;
+  double scale;
 };
 
 constexpr int AGG_AVG = 4;
@@ -59,6 +64,7 @@ struct RParams {                   // rekey_minmax: per-glob uncollapsed table -
   unsigned long long stride[MAXSTR];
   unsigned long long ndim[MAXSTR];
   const uint32_t* map[MAXSTR];     // dim id -> collapsed dim id (null: identity)
+  uint32_t exist_cnt;              // as FParams::exist_cnt
 };
 
 hipError_t launch_rekey_minmax(const RParams& R, hipStream_t stream);
@@ -102,6 +108,8 @@ struct SParams {
   const uint32_t* name_rank;
   int64_t bucket_base;
   int64_t step;
+  uint32_t exist_cnt;              // as FParams::exist_cnt / scale
+  double scale;
 };
 // Workspace bytes launch_finalize_sparse needs for `n` occupied slots (sort buffers + scan + sort temp).
 size_t sparse_workspace_bytes(unsigned long long n, int end_bit);
@@ -165,6 +173,13 @@ struct XParams {
   int agg;                         // Agg (kernel aggregate)
   int hash;                        // q's table is the hash-mode table
   QParams q;
+  // AGG, field charts: `<field> IS NOT NULL` is a conjunct -- a row whose value column (query column 1) is NULL or
+  // absent does not pass.  A segment whose column 1 is VARCHAR (QCol.pad & VCONV_TEXT) decodes the dictionary code
+  // and, once the row passes, reads its double from ftab[global id] and its validity from bit (global id) of fok
+  // (text that casts to NULL keeps the row, with a NULL value).
+  uint32_t field;
+  const double* ftab;
+  const uint32_t* fok;
   // TAGNUM: the tag's query column (its QCol.pad: Parquet type | glob union type << 8), per-glob tables of tcap slots
   // (keys TAG_EMPTY-initialised, 64-bit counts), per-glob [NULL rows, all-ones-key rows], overflow flag
   uint32_t tag_qc;

@@ -98,6 +98,9 @@ struct QCol {               // one query column in one segment
 // Value column of a segment whose glob unifies it to FLOAT while the file stores integers (union_by_name): the value
 // is cast to FLOAT (round to nearest) before it is aggregated.
 constexpr uint32_t VCONV_VIA_FLOAT = 0x100u;
+// Value column of a field chart stored as VARCHAR (dictionary codes): the general row scan reads the value of a code
+// from the query's per-dictionary-id table (XParams::ftab / fok).
+constexpr uint32_t VCONV_TEXT = 0x200u;
 
 struct QSeg {
   const uint8_t* base;

@@ -87,7 +87,8 @@ Request parse_request(const std::string& text) {
     if (const Json* a = c->get("aggregation"); a && a->is_str()) r.aggregation = a->str;
     if (const Json* ro = c->get("rollup"); ro && ro->is_str()) r.rollup = ro->str;
     if (const Json* t = c->get("type"); t && t->is_str()) r.chart_type = t->str;
-    if (const Json* f = c->get("fieldName"); f && !f->is_null()) r.field_chart = true;
+    if (const Json* f = c->get("fieldName"); f && !f->is_null()) r.field_name = f->is_str() ? f->str : f->scalar_text();
+    if (const Json* f = c->get("fieldType"); f && !f->is_null()) r.field_type = f->is_str() ? f->str : f->scalar_text();
   }
   if (const Json* x = be->get("extract"); x && !x->is_null()) r.has_extract = true;
   if (const Json* x = be->get("compute"); x && !x->is_null()) r.has_compute = true;
@@ -152,6 +153,7 @@ void leaf_keys(const FilterNode* n, std::vector<std::string>& out) {
 }
 
 std::string value_column(const Request& r) {
+  if (r.field_name && r.field_type) return *r.field_name + "$" + *r.field_type;
   if (r.dataset == "metrics") return "rollup_" + (r.rollup.empty() ? std::string("sum") : r.rollup);
   return kValue;
 }
@@ -209,7 +211,8 @@ Request copy_request(const Request& r) {
   c.group_bys = r.group_bys;
   c.chart_type = r.chart_type;
   c.rollup = r.rollup;
-  c.field_chart = r.field_chart;
+  c.field_name = r.field_name;
+  c.field_type = r.field_type;
   c.has_extract = r.has_extract;
   c.has_compute = r.has_compute;
   c.limit = r.limit;

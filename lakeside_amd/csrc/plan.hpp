@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <map>
 #include <memory>
+#include <optional>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -48,7 +49,11 @@ struct Request {
   std::vector<std::string> group_bys;
   std::string chart_type = "count";
   std::string rollup;            // empty = none
-  bool field_chart = false, has_extract = false, has_compute = false;
+  // chart.fieldName / chart.fieldType (BaseExpr.scala:355-367): the chart aggregates the numeric field
+  // `<fieldName>$<fieldType>` of the rows instead of `_cardinalhq.value`.  A JSON null counts as absent.
+  std::optional<std::string> field_name, field_type;
+  bool field_chart() const { return field_name.has_value(); }
+  bool has_extract = false, has_compute = false;
   // exemplar queries (no chart): ORDER BY "_cardinalhq.timestamp" <order> LIMIT <limit> (BaseExpr.scala:234-239;
   // defaults ASTUtils.scala:360-361)
   int64_t limit = 1000;
@@ -71,7 +76,8 @@ Request copy_request(const Request& r);
 std::set<std::string> field_set(const Request& r);
 // Every leaf key, including those under NOT (the generated SQL references all of them).
 void leaf_keys(const FilterNode* n, std::vector<std::string>& out);
-// Aggregated column: logs/traces `_cardinalhq.value`; metrics rollup_<rollup|sum> (BaseExpr.scala:349-394).
+// Aggregated column: logs/traces `_cardinalhq.value`; metrics rollup_<rollup|sum> (BaseExpr.scala:349-394); a field
+// chart's `<fieldName>$<fieldType>` (BaseExpr.scala:357-362).
 std::string value_column(const Request& r);
 // Column restricted to a finite value list by an eq/in leaf on the top-level AND chain (so every
 // passing row carries one of those values); empty if none.

@@ -79,12 +79,17 @@ def segment_request(index: int, step: int = 60000, hour: int = None, query_tags=
             "collectorId": "k", "bucketName": "b", "cName": "", "startTs": start, "endTs": start + HOUR}
 
 
-def pushdown(filter_, segs, agg="sum", group_bys=(), dataset="logs", tag=None) -> dict:
+def pushdown(filter_, segs, agg="sum", group_bys=(), dataset="logs", tag=None, field=None) -> dict:
     """A PushDownRequest; with `tag`, a tag query (no chart, isTagQuery + tagDataType, as
-    QueryEngineV2.evaluateTagQuery sends it)."""
+    QueryEngineV2.evaluateTagQuery sends it); with `field` = (fieldName, fieldType), a field chart: the aggregate of
+    the rows' `<fieldName>$<fieldType>` column (fieldType None: the key is left out)."""
     be = {"id": "A", "dataset": dataset, "filter": filter_,
           "chart": {"aggregation": agg, "groupBys": list(group_bys), "type": "count"},
           "limit": 1000, "order": "DESC", "metricType": "gauge", "returnResults": True}
+    if field is not None:
+        be["chart"]["fieldName"] = field[0]
+        if field[1] is not None:
+            be["chart"]["fieldType"] = field[1]
     req = {"baseExpr": be, "segmentRequests": list(segs), "reverseSort": False, "isTagQuery": False}
     if tag is not None:
         del be["chart"]
