@@ -13,16 +13,20 @@ SYNTH   = lakeside_amd/liblakeside_synth.so
 RELIB   = lakeside_amd/liblakeside_regex.so
 TXLIB   = lakeside_amd/liblakeside_text.so
 
-HOST_SRCS = $(SRC)/numleaf.cpp $(SRC)/exemplar.cpp $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/ddsketch.cpp $(SRC)/hll.cpp $(SRC)/regex.cpp $(SRC)/codec.cpp $(SRC)/parquet.cpp $(SRC)/plan.cpp $(SRC)/loader.cpp $(SRC)/engine.cpp $(SRC)/eval.cpp $(SRC)/dims.cpp $(SRC)/comm.cpp $(SRC)/abi.cpp
+HOST_SRCS = $(SRC)/numleaf.cpp $(SRC)/exemplar.cpp $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/formula_eval.cpp $(SRC)/ddsketch.cpp $(SRC)/hll.cpp $(SRC)/regex.cpp $(SRC)/codec.cpp $(SRC)/parquet.cpp $(SRC)/plan.cpp $(SRC)/loader.cpp $(SRC)/engine.cpp $(SRC)/eval.cpp $(SRC)/dims.cpp $(SRC)/comm.cpp $(SRC)/abi.cpp
 HOST_OBJS = $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(HOST_SRCS))
 # the fused scan kernels: one unit per (aggregate, kernel family, table mode) so they compile in parallel
 SCAN_LEAN  = $(foreach a,sum min max count,$(foreach m,d h,$(OBJDIR)/scan_$(a)_lean_$(m).o))
 SCAN_TILES = $(foreach a,sum min max count,$(foreach m,d h,$(OBJDIR)/scan_$(a)_tiles_$(m).o))
-HIP_OBJS  = $(OBJDIR)/kernels.o $(OBJDIR)/ex_kernels.o $(SCAN_LEAN) $(SCAN_TILES)
+HIP_OBJS  = $(OBJDIR)/kernels.o $(OBJDIR)/ex_kernels.o $(OBJDIR)/formula_kernels.o $(SCAN_LEAN) $(SCAN_TILES)
 HDRS = $(wildcard $(SRC)/*.hpp) $(SRC)/unicode_tables.inc include/lakeside_gpu.h include/lakeside_regex.h include/lakeside_text.h
 # device code includes only these (host-only header edits do not rebuild the kernels); lean_kernel.hpp only the
 # scan_lean units, scan_kernel.hpp only the scan units
 DEV_HDRS = $(SRC)/device_common.hpp $(SRC)/kernels.hpp $(SRC)/layout.hpp $(SRC)/scan_inst.hpp
+# the formula kernels: correctly rounded IEEE double, one operation at a time (no contraction; they use no atomics on
+# floating point, so -munsafe-fp-atomics selects nothing in this unit)
+$(OBJDIR)/formula_kernels.o: HIPFLAGS += -ffp-contract=off
+$(OBJDIR)/formula_kernels.o: $(SRC)/formula_cell.hpp $(SRC)/formula_kernels.hpp
 
 all: $(LIB) $(SYNTH) $(RELIB) $(TXLIB)
 
@@ -44,9 +48,10 @@ $(LIB): $(HOST_OBJS) $(HIP_OBJS)
 $(RELIB): $(SRC)/regex.cpp $(SRC)/regex_capi.cpp $(SRC)/regex.hpp $(SRC)/unicode_tables.inc include/lakeside_regex.h
 	g++ $(CXXFLAGS_HOST) -shared -o $@ $(SRC)/regex.cpp $(SRC)/regex_capi.cpp
 
-# host-only Java 17 number text and the field charts' text -> double classifier (CPU differential tests)
-$(TXLIB): $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/evalutil.hpp include/lakeside_text.h
-	g++ $(CXXFLAGS_HOST) -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -shared -o $@ $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp
+# host-only Java 17 number text, the field charts' text -> double classifier and the formula parser / cell function
+# (CPU differential tests)
+$(TXLIB): $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/formula.hpp $(SRC)/formula_cell.hpp $(SRC)/evalutil.hpp include/lakeside_text.h
+	g++ $(CXXFLAGS_HOST) -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -shared -o $@ $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp
 
 $(SYNTH): tools/synth.cpp $(SRC)/thrift.hpp
 	g++ -O3 -std=c++17 -fPIC -shared -pthread -Wall -o $@ tools/synth.cpp

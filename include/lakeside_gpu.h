@@ -50,7 +50,7 @@ enum {
                                  (lk_result_stats "plan_bytes"; measurement only, costs ~5% of scan time) */
 
 /* options_json: {"device": 0, "hbm_budget_bytes": N, "max_calls": 4, "dict_compact_min_dead": 1024,
- *                "load_threads": 0}; NULL = defaults.
+ *                "load_threads": 0, "formula_dense_max_cells": 4194304, "formula_hash_slots": 0}; NULL = defaults.
  * hbm_budget_bytes: weight bound of the HBM segment cache (the worker's Caffeine cache weight,
  * query-worker/.../WorkerApi.scala:53-64): inserting past it evicts least-recently-used segments; 0 (default) = no
  * bound, eviction only when HBM runs out.  max_calls: evaluations in flight (one stream each).
@@ -88,6 +88,26 @@ int lk_engine_drop_caches(lk_engine* e);
  * flags: LK_PER_GLOB_ROWS or LK_MERGED. */
 int lk_eval_pushdown(lk_engine* e, const char* push_down_json, const char* const* paths, size_t n_paths,
                      int glob_size, unsigned flags, lk_result** out);
+
+/* QueryEngineV2.evaluateFormula for one SegmentGroup (query-api/.../engine/QueryEngineV2.scala:310-389): arithmetic
+ * over several base expressions, e.g. an error rate a / b * 100, joined per (timestamp, group key) on the device.
+ * formula_json: {"formula": "a / b * 100",
+ *                "expressions": {"a": {"pushDown": <PushDownRequest, as lk_eval_pushdown takes>, "paths": [..]},
+ *                                "b": {...}}}
+ * Only the expressions the formula references are evaluated; a formula without a variable (5 + 3) gives LK_OK and no
+ * rows.  Rows: merged, ascending timestamp (order within one timestamp unspecified); value = the formula's value; tags =
+ * those of the row the value takes its tags from (Formula.scala:32-69: e1's, e2's where an addition filled e1; a constant
+ * has none without groupBys).  The tag columns are the union of the referenced expressions' tag columns in order of
+ * first appearance; a row with empty tags answers NULL in every column.  lk_result_globs is all zeros.  The bulk tag
+ * export does not apply to formula results: lk_result_group_ids returns NULL and lk_result_num_group_columns 0 -- read
+ * tags with lk_result_tag_value.  lk_result_stats carries "formula": {"mode": "dense"|"hash", "cells", "operands_on_device",
+ * "operands_uploaded", "regrows"}.
+ * LK_ERR_ARG: malformed formula (unknown variable, unbalanced parentheses, a single term), expressions with different
+ * steps.  LK_ERR_UNSUPPORTED (the message names the rule): `^`, relational operators, unary signs; expressions whose
+ * groupBy sets differ; an expression without a chart, a tag query, extract / compute, metrics percentiles.
+ * Engine options: cell spaces (buckets x union groups) up to "formula_dense_max_cells" use a dense cell table, larger
+ * ones a hash table of "formula_hash_slots" slots to begin with (0: sized from the operands' rows) that regrows when full. */
+int lk_eval_formula(lk_engine* e, const char* formula_json, int glob_size, lk_result** out);
 
 size_t lk_result_num_rows(const lk_result* r);
 const int64_t* lk_result_timestamps(const lk_result* r);   /* ascending (ties: glob, then group order) */

@@ -5,6 +5,7 @@
 #ifndef LAKESIDE_TEXT_H
 #define LAKESIDE_TEXT_H
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -19,6 +20,19 @@ int lk_java_float_text(float x, char* buf, size_t cap);
  * cast is NULL (the first byte is an ASCII letter other than i I n N); -1 for every other text, which the evaluator
  * refuses (LK_ERR_UNSUPPORTED) instead of guessing DuckDB's cast.  out may be NULL. */
 int lk_field_number(const char* s, size_t n, double* out);
+
+/* Formulas over DataExprs (lk_eval_formula, include/lakeside_gpu.h), the host-only parts (lakeside_amd/csrc/formula.cpp,
+ * formula_cell.hpp).  lk_formula_plan parses `formula` over the n variables `names` and writes its postfix program into
+ * out (NUL-terminated, truncated to cap): one token per operation, `$<i>` = variable names[i], a constant as Java's
+ * Double.toString prints it, `+ - * /`.  Returns 0; -1 (LK_ERR_ARG: unknown variable, unbalanced parentheses, a single
+ * term, malformed text) or -2 (LK_ERR_UNSUPPORTED: `^`, relational operators, unary signs) with the reason in out. */
+int lk_formula_plan(const char* formula, const char* const* names, size_t n, char* out, size_t cap);
+/* Runs the formula's program over ncells cells with the function the GPU kernels compile (fx_eval_cell).  Per cell c
+ * and variable i (n <= 8): present[c * n + i] (0 / 1), value[c * n + i], src[c * n + i] (the tag source handed through).
+ * Per cell: out_present, out_value, out_src (-1: a constant's tags).  Returns 0 or lk_formula_plan's error. */
+int lk_formula_eval_cell(const char* formula, const char* const* names, size_t n, size_t ncells, const uint8_t* present,
+                         const double* value, const int32_t* src, uint8_t* out_present, double* out_value,
+                         int32_t* out_src);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@ SIGNATURES = [
     ("lk_engine_drop_caches", _c.c_int, [_P]),
     ("lk_eval_pushdown", _c.c_int, [_P, _c.c_char_p, _c.POINTER(_c.c_char_p), _c.c_size_t, _c.c_int, _c.c_uint,
                                     _c.POINTER(_P)]),
+    ("lk_eval_formula", _c.c_int, [_P, _c.c_char_p, _c.c_int, _c.POINTER(_P)]),
     ("lk_result_num_rows", _c.c_size_t, [_P]),
     ("lk_result_timestamps", _c.POINTER(_c.c_int64), [_P]),
     ("lk_result_values", _c.POINTER(_c.c_double), [_P]),

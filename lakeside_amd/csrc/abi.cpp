@@ -14,6 +14,7 @@
 namespace lk {
 int evaluate(Engine& E, const std::string& json, const char* const* paths, size_t n_paths, int glob_size,
              unsigned flags, const int32_t* shard, bool dist, lk_result* res);
+int evaluate_formula(Engine& E, const std::string& json, int glob_size, lk_result* res);
 }
 
 namespace {
@@ -70,6 +71,10 @@ int lk_engine_create(const char* options_json, lk_engine** out) {
           e->e->compact_min_dead = size_t(std::max<int64_t>(1, d->as_i64()));
         if (const lk::Json* t = o.get("load_threads"))
           e->e->load_threads = int(std::min<int64_t>(64, std::max<int64_t>(0, t->as_i64())));
+        if (const lk::Json* c = o.get("formula_dense_max_cells"))
+          e->e->formula_dense_max_cells = uint64_t(std::max<int64_t>(0, c->as_i64()));
+        if (const lk::Json* c = o.get("formula_hash_slots"))
+          e->e->formula_hash_slots = uint64_t(std::min<int64_t>(int64_t(1) << 32, std::max<int64_t>(0, c->as_i64())));
       }
     } catch (...) {
       delete e;
@@ -222,6 +227,24 @@ int lk_eval_pushdown(lk_engine* e, const char* push_down_json, const char* const
 int lk_eval_pushdown_dist(lk_engine* e, const char* push_down_json, const char* const* paths, size_t n_paths,
                           const int32_t* shard, int glob_size, lk_result** out) {
   return eval_common(e, push_down_json, paths, n_paths, shard, glob_size, LK_MERGED, true, out);
+}
+
+int lk_eval_formula(lk_engine* e, const char* formula_json, int glob_size, lk_result** out) {
+  if (!e || !formula_json || !out) return LK_ERR_ARG;
+  *out = nullptr;
+  return guarded([&] {
+    e->e->maybe_compact();
+    std::shared_lock<std::shared_mutex> gen(e->e->gen_mu);
+    auto* r = new lk_result();
+    try {
+      lk::evaluate_formula(*e->e, formula_json, glob_size, r);
+    } catch (...) {
+      delete r;
+      throw;
+    }
+    *out = r;
+    return LK_OK;
+  });
 }
 
 size_t lk_result_num_rows(const lk_result* r) { return r ? r->nrows : 0; }

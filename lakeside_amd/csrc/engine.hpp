@@ -138,6 +138,11 @@ struct FieldTab {
 struct Engine {
   int device = 0;
   size_t max_calls = 4;                          // evaluation contexts (streams) in flight
+  // lk_eval_formula: cell spaces (buckets x union groups) up to this many cells use a dense cell table, larger ones an
+  // open-addressing hash table of formula_hash_slots slots to begin with (0: twice the operands' rows), which
+  // regrows fourfold when it fills past three quarters
+  uint64_t formula_dense_max_cells = uint64_t(1) << 22;
+  uint64_t formula_hash_slots = 0;
   std::mutex ctx_mu;
   std::condition_variable ctx_cv;
   std::vector<std::unique_ptr<CallCtx>> ctx_free;
@@ -298,7 +303,13 @@ struct lk_result {
   lk_result() = default;
   lk_result(const lk_result&) = delete;
   lk_result& operator=(const lk_result&) = delete;
-  ~lk_result() { lk::pinned_release(blk); }
+  ~lk_result() {
+    if (dev_rows) (void)hipFree(dev_rows);
+    lk::pinned_release(blk);
+  }
+  // internal (operands of lk_eval_formula, kEvalKeepDevice): the finalized rows stay on the device, columns
+  // [ts 8 B | value 8 B | group id 4 B] x nrows in one allocation owned by this result; ts / val / gid stay null.
+  void* dev_rows = nullptr;
   // with_glob = false (merged rows: every glob index is 0): the glob column is a shared read-only block of
   // zeros, so the device writes 20 instead of 24 bytes per row over the host link.
   void alloc_rows(size_t n, bool with_glob = true) {
@@ -346,11 +357,22 @@ struct lk_result {
       if (kv.first == col) return kv.second;
     return nullptr;
   }
+  // The tag of a merged row given by its group id alone (formula results name their rows' tags by operand and group id).
+  const char* tag_of_gid(uint32_t g, size_t col) const {
+    if (col < tcols.size()) return own_tag_gid(g, col);
+    for (size_t c = 0; c < tcols.size(); c++)
+      if (own_tag_gid(g, c)) return nullptr;
+    if (qt_of_glob.empty()) return nullptr;
+    for (auto& kv : qt_of_glob[0])
+      if (kv.first == col) return kv.second;
+    return nullptr;
+  }
+  const char* own_tag(size_t row, size_t c) const { return own_tag_gid(gid[row], c); }
   // S15 (Commons.scala:433): NULL, "null" and "" drop the tag
-  const char* own_tag(size_t row, size_t c) const {
+  const char* own_tag_gid(uint32_t g, size_t c) const {
     const TagCol& t = tcols[c];
     if (t.hidden) return nullptr;
-    const uint32_t d = uint32_t((gid[row] / t.stride) % t.ndim);
+    const uint32_t d = uint32_t((g / t.stride) % t.ndim);
     if (d == t.dim_null) return t.null_value;
     if (t.shared) return (*t.shared)[d];
     if (!t.local.empty()) return t.local[d];

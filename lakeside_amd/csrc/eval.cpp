@@ -380,6 +380,11 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
                          int glob_size, unsigned flags, const int32_t* shard, bool dist, lk_result* res, unsigned redo);
 // internal evaluation flag: per-glob rows of a distributed call (rank 0 receives them), for evaluate_metrics_pct
 constexpr unsigned kEvalDistPerGlob = 1u << 30;
+// internal evaluation flag (evaluate_keep_device, the operands of lk_eval_formula): merged rows finalized into a device
+// buffer the result owns (lk_result::dev_rows) instead of the host block -- no speculative finalize, no small-table
+// epilogue, no key_bits / ts_runs host expansion, no device->host copy.  Off for every C ABI entry point but
+// lk_eval_formula.
+constexpr unsigned kEvalKeepDevice = 1u << 29;
 static int evaluate_metrics_pct(Engine& E, const std::string& json, const Request& R, const char* const* paths,
                                 size_t n_paths, int glob_size, unsigned flags, const int32_t* shard, bool dist,
                                 lk_result* res);
@@ -1806,7 +1811,10 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   // come back with one stream synchronization instead of three (scan flags, row count, rows).  A re-run (metrics off
   // the step grid, MIN over NaN) discards the speculative rows.
   const uint64_t out_keys = ncells == 0 ? 0 : (per_glob_rows ? ncells : (collapse ? nbuckets : nbuckets * ngroups));
-  const bool fast_final = !dist && !hash_mode && !sketch && !ces && !rekey && ncells && out_keys <= (uint64_t(1) << 20) &&
+  const bool keep_dev = (flags & kEvalKeepDevice) != 0;
+  if (keep_dev && (dist || per_glob_rows || sketch || ces || tagq))
+    throw PlanError(LK_ERR_DEVICE, "internal: rows kept on the device are merged aggregate rows");
+  const bool fast_final = !keep_dev && !dist && !hash_mode && !sketch && !ces && !rekey && ncells && out_keys <= (uint64_t(1) << 20) &&
                           !getenv("LK_NO_FAST_FINAL");
   // field charts: `<field> IS NOT NULL` drops a row, so a cell exists iff a row with a field reached it.  The row
   // scan applies the conjunct per row (rows != 0 says so); the fused kernels count every passing row, and a numeric
@@ -2420,7 +2428,7 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
     if (fast_done) {
       nrows_out = fast_rows;   // rows already in the result block (speculative finalize behind the scan)
     } else if (emit && F.nkeys) {
-      if (key_rows_ok && F.nkeys == okeys && !F.key_base) F.key_bits = reinterpret_cast<unsigned long long*>(hbuf + o_kbits);
+      if (!keep_dev && key_rows_ok && F.nkeys == okeys && !F.key_base) F.key_bits = reinterpret_cast<unsigned long long*>(hbuf + o_kbits);
       HIP_TRY(launch_finalize_count(F, d_counts, st));
       HIP_TRY(hipMemcpyAsync(&nrows_out, d_counts + nfb, 4, hipMemcpyDeviceToHost, st));
     }
@@ -2472,6 +2480,7 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   if (!fast_done) HIP_TRY(hipStreamSynchronize(st));
   const double sync_ms = ms_since(t_start);     // scan + merge + finalize done
   if (fast_done) res->nrows = nrows_out;       // the block holds out_keys rows' room; nrows_out of them are written
+  else if (keep_dev) res->nrows = nrows_out;   // (the rows stay on the device: below)
   else if (!rows_done) res->alloc_rows(nrows_out, per_glob_rows);
   const double alloc_ms = ms_since(t_start);
   if (ces) {
@@ -2492,6 +2501,18 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
       if (per_glob_rows) res->glob[r] = k.glob;
       res->sketches.push_back(k.sk.serialize());
       if (res->keep_sketches) res->dd_objs.push_back(k.sk);
+    }
+  } else if (keep_dev) {
+    if (nrows_out) {
+      const size_t n = nrows_out;
+      HIP_TRY(hipMalloc(&res->dev_rows, n * 20 + 64));
+      uint8_t* ob = static_cast<uint8_t*>(res->dev_rows);
+      int64_t* o_ts = reinterpret_cast<int64_t*>(ob);
+      double* o_val = reinterpret_cast<double*>(ob + n * 8);
+      uint32_t* o_gid = reinterpret_cast<uint32_t*>(ob + n * 16);
+      if (hash_mode) HIP_TRY(launch_sparse_write(S, nocc, sws, o_ts, o_val, o_gid, nullptr, st));
+      else HIP_TRY(launch_finalize_write(F, d_counts, o_ts, o_val, o_gid, nullptr, st));
+      HIP_TRY(hipStreamSynchronize(st));
     }
   } else if (nrows_out && !rows_done && !fast_done) {
     // Rows written by the kernel straight into the mapped pinned result block when it is pinned: no device->host
@@ -2659,6 +2680,12 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   if (dense_shape) res->stats += ",\"lean_dense_shape\":1";
   res->stats += "}";
   return LK_OK;
+}
+
+// Operand of a formula (formula_eval.cpp): one merged evaluation whose rows stay on the device (kEvalKeepDevice).
+int evaluate_keep_device(Engine& E, const std::shared_ptr<const Request>& Rp, const char* const* paths, size_t n_paths,
+                         int glob_size, lk_result* res) {
+  return evaluate_req(E, Rp, paths, n_paths, glob_size, LK_MERGED | kEvalKeepDevice, nullptr, false, res);
 }
 
 }  // namespace lk

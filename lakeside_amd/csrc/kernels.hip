@@ -780,6 +780,12 @@ hipError_t launch_scan(const QParams& P, int agg, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// finalize_scan on its own (the formula kernels' block and bucket counts, formula_kernels.hip)
+hipError_t launch_scan_counts(uint32_t* counts, uint32_t n, hipStream_t st) {
+  hipLaunchKernelGGL(finalize_scan, dim3(1), dim3(1024), 0, st, counts, n);
+  return hipGetLastError();
+}
+
 uint32_t finalize_blocks(unsigned long long nkeys) {
   return uint32_t((nkeys + FB * FITEMS - 1) / (FB * FITEMS));
 }

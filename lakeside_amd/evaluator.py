@@ -173,7 +173,8 @@ class Engine:
     """One per process per GPU: HIP device, stream, HBM segment cache, optional RCCL communicator."""
 
     def __init__(self, device: int = 0, hbm_budget_bytes: int = 0, max_calls: int = 4, dict_compact_min_dead: int = 0,
-                 load_threads: int = 0):
+                 load_threads: int = 0, formula_dense_max_cells: Optional[int] = None,
+                 formula_hash_slots: Optional[int] = None):
         L = _lib.lib()
         h = ctypes.c_void_p()
         opts = {"device": device, "hbm_budget_bytes": int(hbm_budget_bytes), "max_calls": int(max_calls)}
@@ -181,6 +182,10 @@ class Engine:
             opts["dict_compact_min_dead"] = int(dict_compact_min_dead)
         if load_threads:
             opts["load_threads"] = int(load_threads)
+        if formula_dense_max_cells is not None:   # lk_eval_formula: dense cell table up to this many cells
+            opts["formula_dense_max_cells"] = int(formula_dense_max_cells)
+        if formula_hash_slots is not None:        # ... and the hash table's first size beyond it (0: from the rows)
+            opts["formula_hash_slots"] = int(formula_hash_slots)
         check(L.lk_engine_create(json.dumps(opts).encode(), ctypes.byref(h)))
         self._h = h
         self.device = device
@@ -246,6 +251,18 @@ class Engine:
         arr = self._path_array(paths)
         h = ctypes.c_void_p()
         check(L.lk_eval_pushdown(self._h, request_json.encode(), arr, len(paths), glob_size, flags, ctypes.byref(h)))
+        return Result(h)
+
+    def eval_formula(self, formula: str, expressions: Dict[str, dict], glob_size: int = 10) -> Result:
+        """lk_eval_formula: `formula` over `expressions` = {variable: {"pushDown": PushDownRequest (dict or JSON
+        text), "paths": [...]}}; merged rows of the formula's value, joined per (timestamp, group key) on the device."""
+        ex = {}
+        for name, e in expressions.items():
+            pd = e["pushDown"]
+            ex[name] = {"pushDown": json.loads(pd) if isinstance(pd, str) else pd, "paths": list(e["paths"])}
+        h = ctypes.c_void_p()
+        check(_lib.lib().lk_eval_formula(self._h, json.dumps({"formula": formula, "expressions": ex}).encode(),
+                                         glob_size, ctypes.byref(h)))
         return Result(h)
 
     # ---- multi-GPU ----

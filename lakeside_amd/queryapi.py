@@ -17,7 +17,9 @@ into a {sum, count} map, is one scan: the table carries both and the merged valu
 left for the host is O(output rows): the future-timestamp drop, the chart transformer (vectorised), the
 group-key collapse of BaseExpr.eval and the payload.
 """
+import ctypes
 import json
+import os
 import time
 from typing import Callable, Dict, List, Optional, Sequence
 
@@ -171,4 +173,77 @@ def evaluate_base_expr(engine, base_expr: dict, segment_requests: Sequence[dict]
     return eval_merged_rows(base_expr, res.ts, res.values, res.tags, step_ms, now_ms)
 
 
-__all__ = ["clause_string", "label", "group_by_key", "transformer", "eval_merged_rows", "evaluate_base_expr"]
+_TEXT = None
+
+
+def _text_lib():
+    """liblakeside_text.so: the formula parser the engine links and Java's Double.toString (host only)."""
+    global _TEXT
+    if _TEXT is None:
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblakeside_text.so")
+        if not os.path.exists(path):
+            raise ImportError(f"{path} is missing: build it with `make`")
+        L = ctypes.CDLL(path)
+        L.lk_formula_plan.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_char_p,
+                                      ctypes.c_size_t]
+        L.lk_formula_plan.restype = ctypes.c_int
+        _TEXT = L
+    return _TEXT
+
+
+def formula_plan(formula: str, names: Sequence[str]) -> List[str]:
+    """The formula's postfix program over the variables `names` (lk_formula_plan): `$<i>`, a constant as Java prints
+    it, `+ - * /`.  ValueError on a formula the engine refuses."""
+    arr = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
+    out = ctypes.create_string_buffer(8192)
+    rc = _text_lib().lk_formula_plan(formula.encode(), arr, len(names), out, len(out))
+    if rc != 0:
+        raise ValueError(f"formula error {rc}: {out.value.decode()}")
+    return out.value.decode().split(" ")
+
+
+def formula_label(formula: str, base_expressions: Dict[str, dict], tags: Dict[str, str]) -> str:
+    """Formula.label (Formula.scala:71-80): "<e1Label> <op> <e2Label>" with + - * /, recursively and without
+    parentheses; ConstantExpr.label is Java's Double.toString of the value; BaseExpr.label is `label`."""
+    names = list(base_expressions)
+    stack: List[str] = []
+    for tok in formula_plan(formula, names):
+        if tok in ("+", "-", "*", "/"):
+            e2 = stack.pop()
+            e1 = stack.pop()
+            stack.append(f"{e1} {tok} {e2}")
+        elif tok.startswith("$"):
+            stack.append(label(base_expressions[names[int(tok[1:])]], tags))
+        else:
+            stack.append(tok)
+    return stack[0]
+
+
+def evaluate_formula(engine, base_expressions: Dict[str, dict], formula: str,
+                     segment_requests_by_id: Dict[str, Sequence[dict]], paths_by_id: Dict[str, Sequence[str]],
+                     step_ms: int, glob_size: int = 10, now_ms: Optional[int] = None) -> List[dict]:
+    """QueryEngineV2.evaluateFormula (QueryEngineV2.scala:310-389) for one SegmentGroup, then toGenericSSEPayload
+    (400-417) with id = the formula text (387): one lk_eval_formula call -- the base expressions are evaluated and
+    joined per (timestamp, group key) on the device, only the combined rows come back -- then the future-timestamp
+    drop (TimeGroupedSketchAggregator.scala:200-222; the leaf and the formula pass both drop per timestamp, so
+    dropping last is the same) and the payloads.  Payloads of one timestamp come out in key order."""
+    now = int(time.time() * 1000) if now_ms is None else int(now_ms)
+    for be in base_expressions.values():   # the engine applies the leaves' transformers: same step, checked here
+        transformer(be, step_ms)
+    exprs = {}
+    for name, be in base_expressions.items():
+        exprs[name] = {"pushDown": {"baseExpr": be, "segmentRequests": list(segment_requests_by_id[name]),
+                                    "reverseSort": False, "isTagQuery": False},
+                       "paths": list(paths_by_id[name])}
+    res = engine.eval_formula(formula, exprs, glob_size)
+    gbs = sorted({g for be in base_expressions.values() for g in ((be.get("chart") or {}).get("groupBys") or [])})
+    rows = [(int(t), tuple(tg.get(g, "") for g in gbs), float(v), tg)
+            for t, v, tg in zip(res.ts, res.values, res.tags) if int(t) <= now]
+    rows.sort(key=lambda r: (r[0], r[1]))
+    return [{"id": formula, "type": "timeseries",
+             "message": {"timestamp": t, "tags": dict(tg), "value": v, "label": formula_label(formula, base_expressions, tg)}}
+            for t, _, v, tg in rows]
+
+
+__all__ = ["clause_string", "label", "group_by_key", "transformer", "eval_merged_rows", "evaluate_base_expr",
+           "formula_plan", "formula_label", "evaluate_formula"]
