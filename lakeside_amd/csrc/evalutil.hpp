@@ -1,11 +1,17 @@
-// Plan helpers shared by the aggregate evaluator (eval.cpp) and the exemplar path (exemplar.cpp).
+// Plan helpers shared by the aggregate evaluator (eval_plan.cpp, eval.cpp) and the exemplar path (exemplar.cpp);
+// defined in eval_plan.cpp unless noted.
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
+#include <memory>
+#include <mutex>
 #include <string>
+#include <string_view>
 #include <unordered_set>
 #include <vector>
 
+#include "../../include/lakeside_gpu.h"
 #include "engine.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
@@ -19,6 +25,20 @@ struct LeafInfo {
   int index;    // global leaf index
 };
 
+// A string filter column: its leaves and their bits in the global leaf numbering.
+struct LeafCol {
+  std::string name;
+  std::vector<const FilterNode*> leaves;
+  uint32_t lbase = 0, lmask = 0, hmask = 0;
+};
+// The numbered leaves of a filter: string leaves column by column, then the numeric ones; the Kleene program.
+struct LeafNumbering {
+  std::vector<LeafInfo> leaves;
+  std::vector<NumLeaf> nleaves;
+  std::vector<std::string> bad_literal;   // fields whose numeric literal fails the SQL (per glob where they exist)
+  std::vector<uint8_t> prog;
+};
+
 // One leaf on one dictionary value (BaseExpr.scala:470-501).
 bool leaf_eval(const FilterNode& f, const std::string& s, re::Regex* re, const std::unordered_set<std::string>* set);
 // regexp_matches(label, p, 'i') / contains' '.*p.*' as an RE2-semantics matcher (PlanError on a bad pattern).
@@ -29,6 +49,9 @@ void collect_leaves(const FilterNode* n, std::vector<const FilterNode*>& out);
 // Truth table of a postfix program over L leaves: bit (T | F << L) = TRUE.
 std::vector<uint32_t> truth_table(const std::vector<uint8_t>& prog, uint32_t L);
 bool null_like(const std::string& s);
+bool null_like(std::string_view s);
+// Conjuncts of the filter's top-level AND chain (a AND (b AND c) -> a, b, c).
+void conjuncts(const FilterNode* n, std::vector<const FilterNode*>& out);
 // NoisyTagsDropper: tag names dropped from tag-query rows
 bool noisy_tag(const std::string& t);
 double ms_since(std::chrono::steady_clock::time_point t0);
@@ -47,6 +70,57 @@ int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const
 bool numeric_op(const std::string& op);
 double normalized_value(const FilterNode& f);
 NumLeaf make_num_leaf(const FilterNode& f, uint32_t col, uint32_t leaf, bool& bad);
+// Numbers the leaves of `cols` (lbase / lmask / hmask), then the leaves `is_num` takes -- a comparison (make_num_leaf), or
+// any other operator as IS NOT NULL (NUMLEAF_NOTNULL: the exemplar path's numeric tag) -- on their column of `nums`, and
+// compiles the filter; refuses more than LEAF_BITS leaves on a column and a program beyond MAXPROG.
+template <class Col, class IsNum>
+LeafNumbering number_leaves(const FilterNode* filter, const std::vector<const FilterNode*>& all_leaves, IsNum is_num,
+                            const std::vector<std::string>& nums, std::vector<Col>& cols) {
+  LeafNumbering n;
+  for (size_t s = 0; s < cols.size(); s++) {
+    LeafCol& sc = cols[s];
+    if (sc.leaves.size() > size_t(LEAF_BITS)) throw PlanError(LK_ERR_UNSUPPORTED, "too many leaves on one column");
+    sc.lbase = uint32_t(n.leaves.size());
+    for (const FilterNode* l : sc.leaves) {
+      const uint32_t idx = uint32_t(n.leaves.size());
+      n.leaves.push_back(LeafInfo{l, int(s), int(idx)});
+      sc.lmask |= 1u << idx;
+      if (l->op == "has" || l->op == "exists") sc.hmask |= 1u << idx;
+    }
+  }
+  for (auto* l : all_leaves)
+    if (is_num(l)) {
+      const uint32_t idx = uint32_t(n.leaves.size());
+      n.leaves.push_back(LeafInfo{l, -1, int(idx)});
+      const uint32_t col = uint32_t(std::find(nums.begin(), nums.end(), l->k) - nums.begin());
+      bool bad = false;
+      NumLeaf nl{};
+      if (numeric_op(l->op)) {
+        nl = make_num_leaf(*l, col, idx, bad);
+      } else {   // "<tag>" IS NOT NULL
+        nl.col = col;
+        nl.leaf = idx;
+        nl.pad = NUMLEAF_NOTNULL;
+      }
+      n.nleaves.push_back(nl);
+      if (bad) n.bad_literal.push_back(l->k);
+    }
+  postfix(filter, n.leaves, n.prog);
+  if (n.prog.size() > size_t(MAXPROG)) throw PlanError(LK_ERR_UNSUPPORTED, "filter too large");
+  return n;
+}
+
+// Leaf outcomes over a column's dictionary values [0, dict_n) (immutable: StableStrs), cached per (column, leaves) in
+// the engine and extended here over the values added since: a regex runs once per distinct value.  skip[j] != 0: leaf
+// j's pattern is not compiled and its bit stays 0; without `skip` a pattern RE2 rejects throws.  Returns the entry
+// with its lock held.
+struct LockedLeafBits {
+  std::shared_ptr<LeafBits> lb;
+  std::unique_lock<std::mutex> guard;
+};
+LockedLeafBits extend_leaf_bits(Engine& E, const LeafCol& sc, const GlobalDict& gd, uint32_t dict_n,
+                                const std::vector<char>* skip = nullptr);
+
 // Java 17 Double.toString / Float.toString text (jdtoa.cpp).
 std::string java_text(double d);
 std::string java_text(float f);

@@ -35,18 +35,12 @@
 #include "comm.hpp"
 #include "engine.hpp"
 #include "evalutil.hpp"
+#include "hostutil.hpp"
 #include "kernels.hpp"
 #include "layout.hpp"
 #include "parquet.hpp"
 
 namespace lk {
-
-#define XHIP_TRY(x)                                                                             \
-  do {                                                                                          \
-    hipError_t _e = (x);                                                                        \
-    if (_e != hipSuccess)                                                                       \
-      throw PlanError(LK_ERR_DEVICE, std::string("HIP: ") + #x + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 namespace {
 
@@ -405,17 +399,12 @@ int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const
   }
 
   // ---- filter columns (string dictionaries) and the Kleene program ----
-  struct XStr {
-    std::string name;
-    std::vector<const FilterNode*> leaves;
-    uint32_t lbase = 0, lmask = 0, hmask = 0, dict_n = 0;
-  };
-  std::vector<XStr> strs;
+  std::vector<LeafCol> strs;
   for (auto* l : all_leaves) {
     if (num_col(l)) continue;
-    auto it = std::find_if(strs.begin(), strs.end(), [&](const XStr& s) { return s.name == l->k; });
+    auto it = std::find_if(strs.begin(), strs.end(), [&](const LeafCol& s) { return s.name == l->k; });
     if (it == strs.end()) {
-      strs.push_back(XStr{});
+      strs.push_back(LeafCol{});
       strs.back().name = l->k;
       it = strs.end() - 1;
     }
@@ -424,43 +413,15 @@ int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const
   if (2 + strs.size() + nums.size() > size_t(MAXQCOL))
     throw PlanError(LK_ERR_UNSUPPORTED, "too many filter columns in one query");
   for (auto& nm : nums)
-    if (std::find_if(strs.begin(), strs.end(), [&](const XStr& sc) { return sc.name == nm; }) != strs.end())
+    if (std::find_if(strs.begin(), strs.end(), [&](const LeafCol& sc) { return sc.name == nm; }) != strs.end())
       throw PlanError(LK_ERR_UNSUPPORTED, "column " + nm + " used both as a string and as a number");
   if (all_leaves.size() > size_t(MAXLEAF)) throw PlanError(LK_ERR_UNSUPPORTED, "too many filter leaves");
-  std::vector<LeafInfo> leaves;
-  for (size_t s = 0; s < strs.size(); s++) {
-    XStr& sc = strs[s];
-    if (sc.leaves.size() > size_t(LEAF_BITS)) throw PlanError(LK_ERR_UNSUPPORTED, "too many leaves on one column");
-    sc.lbase = uint32_t(leaves.size());
-    for (const FilterNode* l : sc.leaves) {
-      const uint32_t idx = uint32_t(leaves.size());
-      leaves.push_back(LeafInfo{l, int(s), int(idx)});
-      sc.lmask |= 1u << idx;
-      if (l->op == "has" || l->op == "exists") sc.hmask |= 1u << idx;
-    }
-  }
-  std::vector<NumLeaf> nleaves;
-  std::vector<std::string> bad_literal;   // fields whose numeric literal fails the SQL (per glob where they exist)
-  for (auto* l : all_leaves)
-    if (num_col(l)) {
-      const uint32_t idx = uint32_t(leaves.size());
-      leaves.push_back(LeafInfo{l, -1, int(idx)});
-      const uint32_t col = uint32_t(std::find(nums.begin(), nums.end(), l->k) - nums.begin());
-      if (!numeric_op(l->op)) {   // IS NOT NULL on the numeric tag (BaseExpr: "<tag>" IS NOT NULL)
-        NumLeaf nl{};
-        nl.col = col;
-        nl.leaf = idx;
-        nl.pad = NUMLEAF_NOTNULL;
-        nleaves.push_back(nl);
-        continue;
-      }
-      bool bad = false;
-      nleaves.push_back(make_num_leaf(*l, col, idx, bad));
-      if (bad) bad_literal.push_back(l->k);
-    }
-  std::vector<uint8_t> prog;
-  postfix(R.filter.get(), leaves, prog);
-  if (prog.size() > size_t(MAXPROG)) throw PlanError(LK_ERR_UNSUPPORTED, "filter too large");
+  // (the numeric tag's `exists` / `has` leaves number as IS NOT NULL leaves: BaseExpr's "<tag>" IS NOT NULL)
+  const LeafNumbering numbered = number_leaves(R.filter.get(), all_leaves, num_col, nums, strs);
+  const std::vector<LeafInfo>& leaves = numbered.leaves;
+  const std::vector<NumLeaf>& nleaves = numbered.nleaves;
+  const std::vector<std::string>& bad_literal = numbered.bad_literal;   // per glob where the field exists
+  const std::vector<uint8_t>& prog = numbered.prog;
 
   // ---- segments and globs ----
   // A segment that cannot be read (missing, corrupt, a shape the loader does not take) fails its glob's query only:
@@ -519,40 +480,16 @@ int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const
     globs.push_back(std::move(g));
   }
 
-  // ---- per filter column: dictionary value -> leaf bits (cached per (column, leaves) like the aggregate path) ----
+  // ---- per filter column: dictionary value -> leaf bits (cached per (column, leaves) like the aggregate path; a
+  // pattern RE2 rejects throws out of the call) ----
   std::vector<std::vector<uint32_t>> tabs(strs.size());
   for (size_t s = 0; s < strs.size(); s++) {
-    XStr& sc = strs[s];
-    GlobalDict& gd = E.dict(sc.name);
+    GlobalDict& gd = E.dict(strs[s].name);
     std::lock_guard<std::mutex> dg(gd.mu);
-    sc.dict_n = uint32_t(gd.size());
-    std::string key = sc.name;
-    for (const FilterNode* l : sc.leaves) {
-      key += '\x1f';
-      key += l->op;
-      for (auto& v : l->v) {
-        key += '\x1e';
-        key += v;
-      }
-    }
-    std::vector<std::unique_ptr<re::Regex>> rxs(sc.leaves.size());
-    std::vector<std::unique_ptr<std::unordered_set<std::string>>> sets(sc.leaves.size());
-    for (size_t j = 0; j < sc.leaves.size(); j++) {
-      const FilterNode* l = sc.leaves[j];
-      if (l->op == "regex" || l->op == "contains") rxs[j] = std::make_unique<re::Regex>(compile_leaf_regex(*l));
-      if ((l->op == "in" || l->op == "not_in") && l->v.size() > 8)
-        sets[j] = std::make_unique<std::unordered_set<std::string>>(l->v.begin(), l->v.end());
-    }
-    auto lb = E.leaf_bits(key);
-    std::lock_guard<std::mutex> lg(lb->mu);
-    for (uint32_t gid = uint32_t(lb->hit.size()); gid < sc.dict_n; gid++) {
-      uint8_t bits = 0;
-      for (size_t j = 0; j < sc.leaves.size(); j++)
-        if (leaf_eval(*sc.leaves[j], gd[gid], rxs[j].get(), sets[j].get())) bits |= uint8_t(1u << j);
-      lb->hit.push_back(bits);
-    }
-    tabs[s].resize(std::max<uint32_t>(sc.dict_n, 1));
-    for (uint32_t gid = 0; gid < sc.dict_n; gid++) tabs[s][gid] = uint32_t(lb->hit[gid]) << 24;
+    const uint32_t dict_n = uint32_t(gd.size());
+    const LockedLeafBits cached = extend_leaf_bits(E, strs[s], gd, dict_n);
+    tabs[s].resize(std::max<uint32_t>(dict_n, 1));
+    for (uint32_t gid = 0; gid < dict_n; gid++) tabs[s][gid] = uint32_t(cached.lb->hit[gid]) << 24;
   }
 
   // ---- per-segment descriptors ----
@@ -639,7 +576,7 @@ int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const
   if (qsegs.size() > 65535) throw PlanError(LK_ERR_UNSUPPORTED, "more than 65535 segments in one evaluation");
 
   // ---- device staging ----
-  XHIP_TRY(hipSetDevice(E.device));
+  HIP_TRY(hipSetDevice(E.device));
   hipStream_t st = X.stream;
   std::vector<uint32_t> truth;
   if (leaves.size() <= size_t(TT_MAX_LEAVES)) truth = truth_table(prog, uint32_t(leaves.size()));
@@ -717,7 +654,7 @@ int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const
     const uint64_t cap_max = std::max<uint64_t>(1 << 12, pow2(2 * max_rows));
     uint64_t tcap = std::min<uint64_t>(cap_max, uint64_t(1) << 12);
     if (const char* e = getenv("LK_TAGNUM_INIT_SLOTS")) tcap = std::min<uint64_t>(cap_max, pow2(std::max<uint64_t>(64, strtoull(e, nullptr, 10))));
-    XHIP_TRY(hipMemcpyAsync(dbuf, hbuf, stage_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dbuf, hbuf, stage_bytes, hipMemcpyHostToDevice, st));
     P.mode = XMODE_TAGNUM;
     float scan_ms = 0.f;
     int attempts = 0;
@@ -731,16 +668,16 @@ int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const
       P.tspec = reinterpret_cast<unsigned long long*>(tb + ng * tcap * 16);
       P.tflags = reinterpret_cast<uint32_t*>(tb + ng * tcap * 16 + ng * 16);
       P.tcap = tcap;
-      XHIP_TRY(hipMemsetAsync(tb, 0xff, ng * tcap * 8, st));
-      XHIP_TRY(hipMemsetAsync(tb + ng * tcap * 8, 0, ng * tcap * 8 + ng * 16 + 64, st));
-      XHIP_TRY(hipEventRecord(X.ev_scan0, st));
-      XHIP_TRY(launch_ex_scan(P, st));
-      XHIP_TRY(hipEventRecord(X.ev_scan1, st));
+      HIP_TRY(hipMemsetAsync(tb, 0xff, ng * tcap * 8, st));
+      HIP_TRY(hipMemsetAsync(tb + ng * tcap * 8, 0, ng * tcap * 8 + ng * 16 + 64, st));
+      HIP_TRY(hipEventRecord(X.ev_scan0, st));
+      HIP_TRY(launch_ex_scan(P, st));
+      HIP_TRY(hipEventRecord(X.ev_scan1, st));
       uint32_t fl = 0;
-      XHIP_TRY(hipMemcpyAsync(&fl, P.tflags, 4, hipMemcpyDeviceToHost, st));
-      XHIP_TRY(hipStreamSynchronize(st));
+      HIP_TRY(hipMemcpyAsync(&fl, P.tflags, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
       float ms = 0.f;
-      XHIP_TRY(hipEventElapsedTime(&ms, X.ev_scan0, X.ev_scan1));
+      HIP_TRY(hipEventElapsedTime(&ms, X.ev_scan0, X.ev_scan1));
       scan_ms += ms;
       if (!(fl & FLAG_HASH_FULL)) break;
       if (tcap >= cap_max) throw PlanError(LK_ERR_MEMORY, "tag value table full at its bound");
@@ -749,17 +686,17 @@ int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const
     // occupied slots -> (key, count, glob) records; per-glob NULL / all-ones counts
     auto* recs = static_cast<unsigned long long*>(X.workspace("tagrecs", ng * tcap * 24 + 64));
     uint32_t* d_n = reinterpret_cast<uint32_t*>(recs);
-    XHIP_TRY(hipMemsetAsync(d_n, 0, 4, st));
-    XHIP_TRY(launch_tag_compact(P.tkeys, P.tcnt, tcap, uint32_t(ng), recs + 1, d_n, st));
+    HIP_TRY(hipMemsetAsync(d_n, 0, 4, st));
+    HIP_TRY(launch_tag_compact(P.tkeys, P.tcnt, tcap, uint32_t(ng), recs + 1, d_n, st));
     uint32_t nrec = 0;
     std::vector<unsigned long long> spec(ng * 2);
-    XHIP_TRY(hipMemcpyAsync(&nrec, d_n, 4, hipMemcpyDeviceToHost, st));
-    XHIP_TRY(hipMemcpyAsync(spec.data(), P.tspec, ng * 16, hipMemcpyDeviceToHost, st));
-    XHIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&nrec, d_n, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(spec.data(), P.tspec, ng * 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     std::vector<unsigned long long> hrec(size_t(nrec) * 3);
     if (nrec) {
-      XHIP_TRY(hipMemcpyAsync(hrec.data(), recs + 1, size_t(nrec) * 24, hipMemcpyDeviceToHost, st));
-      XHIP_TRY(hipStreamSynchronize(st));
+      HIP_TRY(hipMemcpyAsync(hrec.data(), recs + 1, size_t(nrec) * 24, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
     }
     // per glob: (key, count) in the union type's value order, NULL last
     struct TRow {
@@ -922,21 +859,21 @@ int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const
       hr[3 * ng + gi] = w;
       nb[gi] = span > 0 ? uint32_t((span + w - 1) / w) : 0u;
     }
-    XHIP_TRY(hipMemcpyAsync(first_upload ? dbuf : dbuf + o_rng, first_upload ? hbuf : hbuf + o_rng,
+    HIP_TRY(hipMemcpyAsync(first_upload ? dbuf : dbuf + o_rng, first_upload ? hbuf : hbuf + o_rng,
                             first_upload ? stage_bytes : ng * 32, hipMemcpyHostToDevice, st));
     first_upload = false;
-    XHIP_TRY(hipMemsetAsync(d_hist, 0, ng * XBINS * 4, st));
+    HIP_TRY(hipMemsetAsync(d_hist, 0, ng * XBINS * 4, st));
     P.mode = XMODE_HIST;
     P.nbins = XBINS;
     P.hist = d_hist;
-    XHIP_TRY(hipEventRecord(e0, st));
-    XHIP_TRY(launch_ex_scan(P, st));
-    XHIP_TRY(hipEventRecord(e1, st));
+    HIP_TRY(hipEventRecord(e0, st));
+    HIP_TRY(launch_ex_scan(P, st));
+    HIP_TRY(hipEventRecord(e1, st));
     uint32_t* hh = reinterpret_cast<uint32_t*>(hbuf + o_hist);
-    XHIP_TRY(hipMemcpyAsync(hh, d_hist, ng * XBINS * 4, hipMemcpyDeviceToHost, st));
-    XHIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(hh, d_hist, ng * XBINS * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     float ms = 0.f;
-    XHIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     scan_ms += ms;
     passes++;
     for (size_t gi = 0; gi < ng; gi++) {
@@ -1004,24 +941,24 @@ int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const
       hr[ng + gi] = live ? g.ehi : 0;
     }
     unsigned long long* d_out = static_cast<unsigned long long*>(X.workspace("xcand", total * 16));
-    XHIP_TRY(hipMemcpyAsync(dbuf + o_rng, hbuf + o_rng, ng * 16, hipMemcpyHostToDevice, st));
-    XHIP_TRY(hipMemsetAsync(dbuf + o_n, 0, 8, st));
+    HIP_TRY(hipMemcpyAsync(dbuf + o_rng, hbuf + o_rng, ng * 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dbuf + o_n, 0, 8, st));
     P.mode = XMODE_EMIT;
     P.out = d_out;
     P.cap = uint32_t(total);
-    XHIP_TRY(hipEventRecord(e0, st));
-    XHIP_TRY(launch_ex_scan(P, st));
-    XHIP_TRY(hipEventRecord(e1, st));
+    HIP_TRY(hipEventRecord(e0, st));
+    HIP_TRY(launch_ex_scan(P, st));
+    HIP_TRY(hipEventRecord(e1, st));
     // pinned destinations: a device-to-host copy into pageable memory goes through the runtime's staging buffers
     PinnedTmp eo(total * 16 + 64);
     const unsigned long long* h_out = static_cast<const unsigned long long*>(eo.p());
-    XHIP_TRY(hipMemcpyAsync(eo.p(), d_out, total * 16, hipMemcpyDeviceToHost, st));
-    XHIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(eo.p()) + total * 16, dbuf + o_n, 4, hipMemcpyDeviceToHost, st));
-    XHIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(eo.p(), d_out, total * 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(eo.p()) + total * 16, dbuf + o_n, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     uint32_t got = 0;
     memcpy(&got, static_cast<const uint8_t*>(eo.p()) + total * 16, 4);
     float ms = 0.f;
-    XHIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     scan_ms += ms;
     if (got != total) throw PlanError(LK_ERR_DEVICE, "internal: exemplar candidate count disagrees with the histogram");
     cands.resize(total);
@@ -1097,7 +1034,7 @@ int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const
     memcpy(hg, gcols.data(), gb);
     for (size_t i = 0; i < nsel; i++) reinterpret_cast<unsigned long long*>(hg + gb)[i] = stream[i]->ref;
     uint8_t* dg = static_cast<uint8_t*>(X.workspace("xgather", gb + sb + vb + ob + 1024));
-    XHIP_TRY(hipMemcpyAsync(dg, hg, gb + sb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dg, hg, gb + sb, hipMemcpyHostToDevice, st));
     GParams G{};
     G.cols = reinterpret_cast<const GCol*>(dg);
     G.sel = reinterpret_cast<const unsigned long long*>(dg + gb);
@@ -1105,9 +1042,9 @@ int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const
     G.ncols = uint32_t(ncols);
     G.val = reinterpret_cast<unsigned long long*>(dg + gb + sb);
     G.ok = dg + gb + sb + vb;
-    XHIP_TRY(launch_ex_gather(G, st));
-    XHIP_TRY(hipMemcpyAsync(hg + gb + sb, G.val, vb + ob, hipMemcpyDeviceToHost, st));   // values and ok flags
-    XHIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(launch_ex_gather(G, st));
+    HIP_TRY(hipMemcpyAsync(hg + gb + sb, G.val, vb + ob, hipMemcpyDeviceToHost, st));   // values and ok flags
+    HIP_TRY(hipStreamSynchronize(st));
     memcpy(gval.data(), hg + gb + sb, vb);
     memcpy(gok.data(), hg + gb + sb + vb, ob);
   }

@@ -35,17 +35,11 @@
 #include "evalutil.hpp"
 #include "formula.hpp"
 #include "formula_kernels.hpp"
+#include "hostutil.hpp"
 #include "json.hpp"
 #include "plan.hpp"
 
 namespace lk {
-
-#define HIP_TRY(x)                                                                              \
-  do {                                                                                          \
-    hipError_t _e = (x);                                                                        \
-    if (_e != hipSuccess)                                                                       \
-      throw PlanError(LK_ERR_DEVICE, std::string("HIP: ") + #x + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 int evaluate(Engine& E, const std::string& json, const char* const* paths, size_t n_paths, int glob_size,
              unsigned flags, const int32_t* shard, bool dist, lk_result* res);
