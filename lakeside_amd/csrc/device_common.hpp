@@ -40,6 +40,10 @@ __device__ __forceinline__ void two_sum(double a, double b, double& s, double& e
   double bb = s - a;
   e = (a - (s - bb)) + (b - bb);
 }
+// The double of a compensated sum.  Once the IEEE running sum `hi` is +-inf or NaN (an infinite or NaN value, an
+// overflow), two_sum's error term is NaN and so is `lo`: `hi` alone is the sum then (hi - hi != 0 exactly for
+// +-inf and NaN).
+__device__ __forceinline__ double dd_value(double hi, double lo) { return hi - hi != 0.0 ? hi : hi + lo; }
 
 // ---- wave-uniform values: readfirstlane puts them in SGPRs so branches on them stay scalar ----
 __device__ __forceinline__ uint32_t uni(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }

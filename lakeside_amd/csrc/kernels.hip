@@ -53,10 +53,10 @@ __device__ __forceinline__ double cell_value(const FParams& F, unsigned long lon
   switch (F.agg) {
     case AGG_COUNT: return double(cnt);
     case AGG_ROWS: return double(F.rows[cell]);
-    case AGG_SUM: return cnt ? F.hi[cell] + F.lo[cell] : 0.0;     // NULL -> 0.0 (JDBC getDouble)
+    case AGG_SUM: return cnt ? dd_value(F.hi[cell], F.lo[cell]) : 0.0;     // NULL -> 0.0 (JDBC getDouble)
     case AGG_MIN:
     case AGG_MAX: return cnt ? order_dbl(F.ext[cell]) : 0.0;
-    default: return cnt ? (F.hi[cell] + F.lo[cell]) / double(cnt) : 0.0;   // avg (per-glob only)
+    default: return cnt ? dd_value(F.hi[cell], F.lo[cell]) / double(cnt) : 0.0;   // avg (per-glob only)
   }
 }
 
@@ -120,8 +120,8 @@ __device__ OutRow make_row(const FParams& F, unsigned long long key) {
     }
   }
   if (!o.exists) return o;
-  if (F.agg == AGG_SUM) o.value = hi + lo;
-  else if (F.agg == AGG_AVG) o.value = (hi + lo) / double(cnt);   // merged {sum, count} map: 0/0 = NaN
+  if (F.agg == AGG_SUM) o.value = dd_value(hi, lo);
+  else if (F.agg == AGG_AVG) o.value = dd_value(hi, lo) / double(cnt);   // merged {sum, count} map: 0/0 = NaN
   else if (F.agg == AGG_COUNT) o.value = double(cnt);
   else if (F.agg == AGG_ROWS) o.value = double(nrows);
   else o.value = ext;
@@ -441,8 +441,8 @@ __global__ __launch_bounds__(SB) void runs_write(SParams S, const unsigned long 
       double value;
       if (S.agg == AGG_COUNT) value = double(cnt);
       else if (S.agg == AGG_ROWS) value = double(nrows);
-      else if (S.agg == AGG_SUM) value = cnt ? hi + lo : 0.0;
-      else if (S.agg == AGG_AVG) value = S.per_glob ? (cnt ? (hi + lo) / double(cnt) : 0.0) : (hi + lo) / double(cnt);
+      else if (S.agg == AGG_SUM) value = cnt ? dd_value(hi, lo) : 0.0;
+      else if (S.agg == AGG_AVG) value = S.per_glob ? (cnt ? dd_value(hi, lo) / double(cnt) : 0.0) : dd_value(hi, lo) / double(cnt);
       else if (S.rekey) value = order_dbl(oext);
       else value = ext;
       if (S.scale != 0.0) value /= S.scale;   // field charts: one division of the final double

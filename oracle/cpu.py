@@ -6,6 +6,7 @@ full-size validation of the GPU rows) and checked against oracle/dataexpr.py in 
 Only tests/, bench.py and __graft_entry__.smoke() may import it; the product path never does.
 """
 import ctypes
+import functools
 import math
 import os
 import time
@@ -248,9 +249,20 @@ def evaluate_exemplar_rows(pr: dx.PushDownRequest, glob_size: int, blobs: Sequen
         L.lkcpu_ex_free(h)
 
 
-def _dd(*xs):
-    """Correctly rounded sum of double-double parts (IEEE propagation for non-finite values)."""
-    return math.fsum(xs) if all(math.isfinite(x) for x in xs) else float(np.sum(np.array(xs)))
+def dd_value(hi, lo):
+    """The double of a double-double sum (scalars or arrays): `hi` alone when it is not finite -- it is the IEEE
+    running sum (+-inf, or NaN for inf + -inf), while the TwoSum error behind `lo` is NaN from the first non-finite
+    step on -- else the rounded hi + lo."""
+    if isinstance(hi, np.ndarray) or isinstance(lo, np.ndarray):
+        hi, lo = np.asarray(hi, np.float64), np.asarray(lo, np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            return np.where(np.isfinite(hi), hi + lo, hi)
+    return hi + lo if math.isfinite(hi) else hi
+
+
+def _dd_cells(cs):
+    """Sum of several cells' double-doubles, rounded once; a cell whose hi is not finite adds its hi only."""
+    return dx.exact_sum(np.array([c.hi for c in cs] + [c.lo for c in cs if math.isfinite(c.hi)], np.float64))
 
 
 class CpuCell:
@@ -263,9 +275,9 @@ class CpuCell:
         if self.count == 0:
             return 0.0
         if agg == dx.SUM:
-            return _dd(self.hi, self.lo)
+            return dd_value(self.hi, self.lo)
         if agg == dx.AVG:
-            return _dd(self.hi, self.lo) / self.count
+            return dd_value(self.hi, self.lo) / self.count
         return self.vmin if agg == dx.MIN else self.vmax
 
 
@@ -358,17 +370,17 @@ def merge_glob_cells(pr: dx.PushDownRequest, glob_cells) -> List[Tuple[int, floa
     for k, cs in merged.items():
         tags = min((c.tags for c in cs), key=lambda t: sorted(t.items()))
         if agg == dx.SUM:
-            val = _dd(*[x for c in cs for x in (c.hi, c.lo)]) if any(c.count for c in cs) else 0.0
+            val = _dd_cells(cs) if any(c.count for c in cs) else 0.0
         elif agg == dx.COUNT:
             val = float(sum(c.count for c in cs))
         elif agg == dx.AVG:
             n = sum(c.count for c in cs)
-            s = _dd(*[x for c in cs for x in (c.hi, c.lo)])
+            s = _dd_cells(cs)
             val = s / n if n else math.nan
         elif agg == dx.MIN:
-            val = min(c.agg_value(dx.MIN) for c in cs)
+            val = functools.reduce(dx.java_min, (c.agg_value(dx.MIN) for c in cs))
         else:
-            val = max(c.agg_value(dx.MAX) for c in cs)
+            val = functools.reduce(dx.java_max, (c.agg_value(dx.MAX) for c in cs))
         out.append((cs[0].ts, val, tags))
     out.sort(key=lambda r: (r[0], sorted(r[2].items()), r[1]))
     return out
@@ -534,12 +546,12 @@ def merge_cell_table(t: CellTable, agg: str, has_group_bys: bool):
         for k in range(int(pos.max()) + 1):
             sel = pos == k
             idx = g[sel]
-            for x in (hi[sel], lo[sel]):
-                s, e = _two_sum(acc_hi[idx], x)
-                acc_hi[idx] = s
-                acc_lo[idx] += e
-        with np.errstate(invalid="ignore"):
-            ssum = np.where(np.isfinite(acc_hi), acc_hi + acc_lo, acc_hi)
+            for x in (hi[sel], np.where(np.isfinite(hi[sel]), lo[sel], 0.0)):   # a non-finite hi: its lo is NaN
+                with np.errstate(invalid="ignore", over="ignore"):
+                    s, e = _two_sum(acc_hi[idx], x)
+                    acc_hi[idx] = s
+                    acc_lo[idx] += e
+        ssum = dd_value(acc_hi, acc_lo)
         if agg == dx.SUM:
             val = np.where(total > 0, ssum, 0.0)
         else:
@@ -551,7 +563,12 @@ def merge_cell_table(t: CellTable, agg: str, has_group_bys: bool):
         src = (t.vmin if agg == dx.MIN else t.vmax)[order]
         cell = np.where(cnt > 0, src, 0.0)   # a cell without values reads 0.0 (S15 getDouble of NULL)
         val = np.full(G, np.inf if agg == dx.MIN else -np.inf)
-        (np.minimum if agg == dx.MIN else np.maximum).at(val, g, cell)
+        with np.errstate(invalid="ignore"):
+            (np.minimum if agg == dx.MIN else np.maximum).at(val, g, cell)
+        # zeros: -0.0 < +0.0 in java.lang.Math, while numpy's choice between equal zeros follows the operand order
+        wins = np.zeros(G, bool)
+        np.logical_or.at(wins, g, (cell == 0.0) & (np.signbit(cell) == (agg == dx.MIN)))
+        val = np.where(val == 0.0, np.where(wins == (agg == dx.MIN), -0.0, 0.0), val)
     return out_ts, val, out_key
 
 
@@ -573,7 +590,8 @@ def assert_columns_equal(got, want, agg: str, label: str = ""):
     both_nan = np.isnan(gv) & np.isnan(wv)
     if agg in (dx.SUM, dx.AVG):
         with np.errstate(invalid="ignore"):
-            ok = (gv == wv) | both_nan | (np.abs(gv - wv) <= np.spacing(np.abs(wv)))
+            fin = np.isfinite(wv)   # +-inf / NaN expected: the same, nothing near
+            ok = (gv == wv) | both_nan | (fin & (np.abs(gv - wv) <= np.spacing(np.where(fin, np.abs(wv), 0.0))))
     else:
         ok = ((gv == wv) & (np.signbit(gv) == np.signbit(wv))) | both_nan
     bad = np.nonzero(~ok)[0]

@@ -23,6 +23,7 @@ import json
 import math
 import re
 from dataclasses import dataclass, field
+from fractions import Fraction
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -662,12 +663,27 @@ class Cell:
 
 
 def exact_sum(v: np.ndarray) -> float:
-    """Correctly rounded sum; NaN/Inf follow IEEE."""
+    """Correctly rounded sum; NaN/Inf follow IEEE.  Never raises: where math.fsum
+    overflows on finite inputs, the exact rational sum is rounded once (to +-inf at or beyond 2^1024 - 2^970,
+    the round-to-nearest overflow threshold)."""
     if v is None or len(v) == 0:
         return 0.0
-    if not np.all(np.isfinite(v)):
-        return float(np.sum(v))
-    return math.fsum(v.tolist())
+    v = np.asarray(v, dtype=np.float64)
+    if not np.all(np.isfinite(v)):   # IEEE, whatever the order: a NaN or both infinities -> NaN, else the infinity
+        pos, neg = bool(np.any(v == np.inf)), bool(np.any(v == -np.inf))
+        if bool(np.any(np.isnan(v))) or (pos and neg):
+            return math.nan
+        return math.inf if pos else -math.inf
+    try:
+        return math.fsum(v.tolist())
+    except OverflowError:
+        s = sum(map(Fraction, v.tolist()))
+        if abs(s) >= SUM_OVERFLOW:
+            return math.inf if s > 0 else -math.inf
+        return float(s)   # int / int true division: correctly rounded
+
+
+SUM_OVERFLOW = 2 ** 1024 - 2 ** 970
 
 
 def evaluate_glob(pr: PushDownRequest, seg_idx: Sequence[int], paths: Sequence[str], sources=None,

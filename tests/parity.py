@@ -1,7 +1,7 @@
 """Row comparison used by the parity tests (GPU rows vs oracle / golden rows).
 
 Bar (BASELINE.json north_star): timestamps and tags exact; count/min/max bit-exact; sums (and avg) within
-1 ulp of the correctly rounded value.
+1 ulp of the correctly rounded value; where that value is +-inf or NaN, the same infinity or NaN.
 """
 import math
 
@@ -22,7 +22,8 @@ def assert_rows_equal(got, want, agg, label=""):
         assert g[2] == w[2], f"{label}: row {i} tags {g[2]} vs {w[2]}"
         gv, wv = g[1], w[1]
         if agg in SUM_LIKE:
-            ok = gv == wv or (math.isnan(gv) and math.isnan(wv)) or abs(gv - wv) <= math.ulp(wv)
+            ok = gv == wv or (math.isnan(gv) and math.isnan(wv)) or (
+                math.isfinite(wv) and abs(gv - wv) <= math.ulp(wv))   # +-inf / NaN expected: the same, nothing near
         else:
             ok = (gv == wv and math.copysign(1, gv) == math.copysign(1, wv)) or (math.isnan(gv) and math.isnan(wv))
         assert ok, f"{label}: row {i} at ts={g[0]} tags={g[2]}: value {gv!r} vs expected {wv!r} (agg {agg})"
@@ -101,8 +102,8 @@ def check_columns(engine, req, keys, blobs, glob_size, flags=("per_glob", "merge
             cnt = table.count[sel]
             if agg == dx.COUNT:
                 want = cnt.astype(np.float64)
-            elif agg in (dx.SUM, dx.AVG):   # CpuCell.agg_value: hi + lo is the double-double's rounded sum
-                s = table.hi[sel] + table.lo[sel]
+            elif agg in (dx.SUM, dx.AVG):   # CpuCell.agg_value: the double-double's rounded sum
+                s = lkcpu.dd_value(table.hi[sel], table.lo[sel])
                 want = np.where(cnt > 0, s if agg == dx.SUM else s / np.maximum(cnt, 1), 0.0)
             else:
                 want = np.where(cnt > 0, (table.vmin if agg == dx.MIN else table.vmax)[sel], 0.0)
