@@ -50,8 +50,8 @@ $(RELIB): $(SRC)/regex.cpp $(SRC)/regex_capi.cpp $(SRC)/regex.hpp $(SRC)/unicode
 
 # host-only Java 17 number text, the field charts' text -> double classifier and the formula parser / cell function
 # (CPU differential tests)
-$(TXLIB): $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/formula.hpp $(SRC)/formula_cell.hpp $(SRC)/evalutil.hpp include/lakeside_text.h
-	g++ $(CXXFLAGS_HOST) -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -shared -o $@ $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp
+$(TXLIB): $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/ex_select_sim.cpp $(SRC)/formula.hpp $(SRC)/formula_cell.hpp $(SRC)/evalutil.hpp $(SRC)/ex_select.hpp $(SRC)/kernels.hpp include/lakeside_text.h
+	g++ $(CXXFLAGS_HOST) -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -shared -o $@ $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/ex_select_sim.cpp
 
 $(SYNTH): tools/synth.cpp $(SRC)/thrift.hpp
 	g++ -O3 -std=c++17 -fPIC -shared -pthread -Wall -o $@ tools/synth.cpp

@@ -34,6 +34,15 @@ int lk_formula_eval_cell(const char* formula, const char* const* names, size_t n
                          const double* value, const int32_t* src, uint8_t* out_present, double* out_value,
                          int32_t* out_src);
 
+/* Runs the exemplar row selection (ex_select.hpp) for one glob over the n passing rows' timestamps ts[0..n), with a
+ * CPU histogram standing in for ex_scan HIST: a row counts in a pass iff rlo <= ts < rhi, in bin
+ * clamp((ts - hbase) / hwidth, 0, nb - 1).  tiles: ntiles x (ts_min, ts_max, nrows) zone maps for the probes
+ * (ntiles = 0: no probing).  Writes the emit range [*elo, *ehi), the rows counted in it and the passes taken; limit = 0
+ * (the evaluator opens no such glob): no pass, no rows, the empty range at the ordered end of the window. */
+int lk_ex_select_sim(const int64_t* ts, size_t n, int64_t win_lo, int64_t win_hi, const int64_t* tiles, size_t ntiles,
+                     uint64_t limit, int desc, uint64_t cand_cap, uint64_t probe_rows,
+                     int64_t* elo, int64_t* ehi, uint64_t* count, int* passes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,10 @@
 // (ex_kernels.hip).  Documented choices where the reference is unspecified: rows tied on the timestamp keep file
 // order (segment position in the glob, then row), which DuckDB's ORDER BY leaves open; metrics exemplars (value =
 // getDouble of the name column) fail like the reference's stream does (-> empty).
+//
+// The evaluation is a sequence of stages over the structs below (exemplar_local, in the style of eval_plan.hpp): a
+// stage reads the earlier stages' structs and returns its own.  The selection arithmetic between the HIST passes is
+// ex_select.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +29,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <map>
 #include <set>
 #include <string>
@@ -34,7 +39,9 @@
 #include "../../include/lakeside_gpu.h"
 #include "comm.hpp"
 #include "engine.hpp"
+#include "eval_plan.hpp"
 #include "evalutil.hpp"
+#include "ex_select.hpp"
 #include "hostutil.hpp"
 #include "kernels.hpp"
 #include "layout.hpp"
@@ -70,34 +77,9 @@ int union_type(int a, int b) {
   return pq::FLOAT;
 }
 
-// JDBC getString text of a raw value of physical type `pt` read as union type `ut`.
-std::string value_text(unsigned long long raw, int pt, int ut) {
-  int64_t iv = 0;
-  double dv = 0.0;
-  float fv = 0.0f;
-  switch (pt) {
-    case pq::INT64: iv = int64_t(raw); dv = double(iv); fv = float(iv); break;
-    case pq::INT32: iv = int32_t(uint32_t(raw)); dv = double(iv); fv = float(iv); break;
-    case pq::DOUBLE: memcpy(&dv, &raw, 8); break;
-    case pq::FLOAT: {
-      const uint32_t u = uint32_t(raw);
-      memcpy(&fv, &u, 4);
-      dv = double(fv);
-      break;
-    }
-    case pq::BOOLEAN: return raw ? "true" : "false";
-    default: throw PlanError(LK_ERR_UNSUPPORTED, "exemplar column of an undecoded type");
-  }
-  switch (ut) {
-    case pq::INT64:
-    case pq::INT32: return std::to_string(iv);
-    case pq::FLOAT: return java_text(fv);
-    default: return java_text(dv);
-  }
-}
-
-double value_double(unsigned long long raw, int pt) {
-  switch (pt) {
+// A raw 64-bit word of Parquet physical type `ptype` as a double: DOUBLE / FLOAT bit patterns, INT32 / INT64 values.
+double raw_as_double(unsigned long long raw, int ptype) {
+  switch (ptype) {
     case pq::DOUBLE: {
       double d;
       memcpy(&d, &raw, 8);
@@ -115,21 +97,138 @@ double value_double(unsigned long long raw, int pt) {
   }
 }
 
-struct XGlob {
+// JDBC getString text of a raw value of physical type `pt` read as union type `ut`.
+std::string value_text(unsigned long long raw, int pt, int ut) {
+  int64_t iv = 0;
+  float fv = 0.0f;
+  switch (pt) {
+    case pq::INT64: iv = int64_t(raw); fv = float(iv); break;
+    case pq::INT32: iv = int32_t(uint32_t(raw)); fv = float(iv); break;
+    case pq::DOUBLE: break;
+    case pq::FLOAT: fv = float(raw_as_double(raw, pt)); break;
+    case pq::BOOLEAN: return raw ? "true" : "false";
+    default: throw PlanError(LK_ERR_UNSUPPORTED, "exemplar column of an undecoded type");
+  }
+  switch (ut) {
+    case pq::INT64:
+    case pq::INT32: return std::to_string(iv);
+    case pq::FLOAT: return java_text(fv);
+    default: return java_text(raw_as_double(raw, pt));
+  }
+}
+
+// Rows summed per key, in first-seen order: the first row of a key is kept and `add` folds the later ones into it.
+template <class Row, class Key, class Add>
+std::vector<Row> sum_first_seen(std::vector<Row>& rows, Key key, Add add) {
+  std::vector<Row> out;
+  std::map<decltype(key(rows[0])), size_t> at;
+  for (auto& r : rows) {
+    const auto [it, fresh] = at.emplace(key(r), out.size());
+    if (fresh) out.push_back(std::move(r));
+    else add(out[it->second], r);
+  }
+  return out;
+}
+
+// A test knob of the environment, read on every call (the tests change them between the calls of one process).
+uint64_t env_u64(const char* name, uint64_t dflt, uint64_t floor) {
+  const char* e = getenv(name);
+  return e ? std::max<uint64_t>(floor, strtoull(e, nullptr, 10)) : dflt;
+}
+
+// A pinned host block from the engine's pool for the length of a transfer (returned to the pool on scope exit).
+struct PinnedTmp {
+  HostBlock b;
+  explicit PinnedTmp(size_t n) : b(pinned_acquire(n)) {}
+  ~PinnedTmp() { pinned_release(b); }
+  PinnedTmp(const PinnedTmp&) = delete;
+  PinnedTmp& operator=(const PinnedTmp&) = delete;
+  void* p() const { return b.p; }
+};
+
+// What the request asks for: depends on the request and flags alone.
+struct XShape {
+  bool tagnum = false, logs = false, desc = true, per_glob_rows = false;
+  uint64_t limit = 0;
+  std::string numtag;
+  std::vector<const FilterNode*> all_leaves;
+  std::vector<std::string> nums;   // numeric comparison columns (gt/ge/lt/le, BaseExpr.scala:488-498)
+  // numeric tag: its leaves (query-api's `exists` on the tag) are numeric IS NOT NULL leaves; the tag column is a
+  // numeric column of the scan either way
+  bool num_col(const FilterNode* l) const { return numeric_op(l->op) || (tagnum && l->k == numtag); }
+};
+
+// The filter columns (string dictionaries) and the Kleene program.
+struct XFilter : LeafNumbering {
+  std::vector<LeafCol> strs;
+};
+
+struct XGlob : XSel {
   std::vector<int> segs;
   bool skip = false;
   uint32_t leaf_false = 0;
-  int64_t win_lo = 0, win_hi = 0;
   std::vector<std::string> cols;          // output columns: projection, then the union (file order)
   std::map<std::string, int> types;       // union type per column
-  // selection state
-  bool open = false;
-  std::vector<int64_t> probes;            // ordered-end-first ranges to try before the whole window (zone maps)
-  size_t probe = 0;
-  int64_t hlo = 0, hhi = 0;               // range still being narrowed
-  uint64_t need = 0, above = 0;           // rows still wanted from [hlo, hhi); rows certainly in beyond it
-  int64_t elo = 0, ehi = 0;               // final emit range
-  uint64_t count = 0;                     // rows in the emit range
+  int type_or(const std::string& name, int dflt) const {
+    const auto it = types.find(name);
+    return it == types.end() ? dflt : it->second;
+  }
+};
+
+struct XGlobs {
+  std::vector<std::shared_ptr<Segment>> segs;
+  std::vector<uint8_t> seg_bad;
+  std::vector<XGlob> globs;
+};
+
+// Per-segment descriptors: `qsegs` goes to the device as it is, `meta` runs parallel to it.
+struct XSegMeta {
+  const Segment* seg;
+  uint32_t pos;    // segment position in the glob
+  uint32_t glob;
+};
+struct XSegs {
+  std::vector<QSeg> qsegs;
+  std::vector<XSegMeta> meta;
+  uint64_t rows_scanned = 0;
+  uint32_t max_tiles = 0;
+};
+
+// The per-glob range words of the staged block, [4][ng]: a HIST pass reads all four, TAGNUM and EMIT the range only.
+struct XRanges {
+  int64_t* w = nullptr;
+  size_t ng = 0;
+  int64_t& rlo(size_t g) const { return w[g]; }
+  int64_t& rhi(size_t g) const { return w[ng + g]; }
+  int64_t& hbase(size_t g) const { return w[2 * ng + g]; }
+  int64_t& hwidth(size_t g) const { return w[3 * ng + g]; }
+  void range(size_t g, bool live, int64_t lo, int64_t hi) const {
+    rlo(g) = live ? lo : 0;
+    rhi(g) = live ? hi : 0;
+  }
+};
+
+// The query staged for the device: one pinned block and its device copy, the scan parameters pointing into it.
+struct XDev {
+  hipStream_t st = nullptr;
+  uint8_t *hbuf = nullptr, *dbuf = nullptr;
+  size_t stage_bytes = 0, o_rng = 0, o_n = 0;
+  XRanges rng;                 // host side
+  uint32_t* hist = nullptr;    // host side: the histogram read back each pass
+  uint32_t* d_hist = nullptr;
+  XParams P{};
+  float scan_ms = 0.f;
+  // the scan between the two events, its time added to scan_ms once the caller has synchronized
+  void scan(CallCtx& X) {
+    HIP_TRY(hipEventRecord(X.ev_scan0, st));
+    HIP_TRY(launch_ex_scan(P, st));
+    HIP_TRY(hipEventRecord(X.ev_scan1, st));
+  }
+  void scanned(CallCtx& X) {
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, X.ev_scan0, X.ev_scan1));
+    scan_ms += ms;
+  }
 };
 
 struct Cand {
@@ -140,22 +239,703 @@ struct Cand {
   unsigned long long ref;
 };
 
-}  // namespace
+// ---- the stages, in call order ----
 
-namespace {
-// A pinned host block from the engine's pool for the length of a transfer (returned to the pool on scope exit).
-struct PinnedTmp {
-  HostBlock b;
-  explicit PinnedTmp(size_t n) : b(pinned_acquire(n)) {}
-  ~PinnedTmp() { pinned_release(b); }
-  PinnedTmp(const PinnedTmp&) = delete;
-  PinnedTmp& operator=(const PinnedTmp&) = delete;
-  void* p() const { return b.p; }
+XShape x_gate(const EvalCall& C, const std::string& numtag) {
+  const Request& R = C.R;
+  XShape qs;
+  qs.numtag = numtag;
+  qs.tagnum = !numtag.empty();
+  if (R.has_extract || R.has_compute)
+    throw PlanError(LK_ERR_UNSUPPORTED, "extract / compute exemplar queries are not on the hot path");
+  qs.logs = R.dataset == "logs";
+  if (!qs.tagnum && !qs.logs && R.dataset != "traces") {
+    // metrics: the projection's second column is "_cardinalhq.name" (BaseExpr.scala:41); getDouble of a metric
+    // name fails the stream, which query-api turns into an empty source (QueryEngineV2.scala:141-145)
+    if (R.dataset == "metrics") throw PlanError(LK_ERR_ARG, "metrics exemplar: getDouble of \"_cardinalhq.name\"");
+    throw PlanError(LK_ERR_ARG, "Invalid dataset: " + R.dataset);
+  }
+  std::string order = R.order;
+  for (auto& c : order) c = char(toupper(static_cast<unsigned char>(c)));
+  if (qs.tagnum) order = "DESC";   // (a tag query has no ORDER BY / LIMIT)
+  if (order != "DESC" && order != "ASC") throw PlanError(LK_ERR_ARG, "ORDER BY direction '" + R.order + "'");
+  if (R.limit < 0 && !qs.tagnum) throw PlanError(LK_ERR_ARG, "negative LIMIT");
+  qs.desc = order == "DESC";
+  qs.limit = qs.tagnum ? 0 : uint64_t(R.limit);
+  qs.per_glob_rows = (C.flags & LK_PER_GLOB_ROWS) != 0;
+
+  collect_leaves(R.filter.get(), qs.all_leaves);
+  for (auto* l : qs.all_leaves) {
+    if (l->extracted || l->computed) throw PlanError(LK_ERR_UNSUPPORTED, "extracted/computed filter fields");
+    if (qs.tagnum && l->k == numtag && !numeric_op(l->op) && l->op != "exists" && l->op != "has")
+      throw PlanError(LK_ERR_UNSUPPORTED, "string comparison '" + l->op + "' on the numeric tag column " + numtag);
+    if (qs.num_col(l)) {
+      if (std::find(qs.nums.begin(), qs.nums.end(), l->k) == qs.nums.end()) qs.nums.push_back(l->k);
+      continue;
+    }
+    static const char* ok[] = {"eq", "!=", "in", "not_in", "regex", "contains", "has", "exists"};
+    if (std::none_of(std::begin(ok), std::end(ok), [&](const char* o) { return l->op == o; }))
+      throw PlanError(LK_ERR_ARG, "Invalid operator " + l->op);
+  }
+  if (qs.tagnum && std::find(qs.nums.begin(), qs.nums.end(), numtag) == qs.nums.end()) qs.nums.push_back(numtag);
+  return qs;
+}
+
+// No segments: Commons.scala:393-396, the sentinel DataPoint(-1, -1, {}).
+void sentinel_row(const EvalCall& C, const XShape& qs) {
+  lk_result* res = C.res;
+  if (qs.per_glob_rows) {
+    res->alloc_rows(1);
+    res->ts[0] = -1;
+    res->val[0] = -1.0;
+    res->glob[0] = 0;
+    res->gid[0] = 0;
+  }
+  res->stats = "{\"scan_ms\":0,\"total_ms\":0,\"rows_scanned\":0,\"candidates\":0}";
+}
+
+XFilter x_filter(const EvalCall& C, const XShape& qs) {
+  XFilter fp;
+  std::vector<LeafCol>& strs = fp.strs;
+  for (auto* l : qs.all_leaves) {
+    if (qs.num_col(l)) continue;
+    auto it = std::find_if(strs.begin(), strs.end(), [&](const LeafCol& s) { return s.name == l->k; });
+    if (it == strs.end()) {
+      strs.push_back(LeafCol{});
+      strs.back().name = l->k;
+      it = strs.end() - 1;
+    }
+    it->leaves.push_back(l);
+  }
+  if (2 + strs.size() + qs.nums.size() > size_t(MAXQCOL))
+    throw PlanError(LK_ERR_UNSUPPORTED, "too many filter columns in one query");
+  for (auto& nm : qs.nums)
+    if (std::find_if(strs.begin(), strs.end(), [&](const LeafCol& sc) { return sc.name == nm; }) != strs.end())
+      throw PlanError(LK_ERR_UNSUPPORTED, "column " + nm + " used both as a string and as a number");
+  if (qs.all_leaves.size() > size_t(MAXLEAF)) throw PlanError(LK_ERR_UNSUPPORTED, "too many filter leaves");
+  // (the numeric tag's `exists` / `has` leaves number as IS NOT NULL leaves: BaseExpr's "<tag>" IS NOT NULL)
+  static_cast<LeafNumbering&>(fp) = number_leaves(
+      C.R.filter.get(), qs.all_leaves, [&](const FilterNode* l) { return qs.num_col(l); }, qs.nums, strs);
+  return fp;
+}
+
+// Segments and globs.  A segment that cannot be read (missing, corrupt, a shape the loader does not take) fails its
+// glob's query only: that glob is empty, the others stream (Commons.scala:249-253, 338-340).
+XGlobs x_globs(const EvalCall& C, const XShape& qs, const XFilter& fp) {
+  const Request& R = C.R;
+  const std::string& numtag = qs.numtag;
+  XGlobs gp;
+  gp.segs.resize(C.n_paths);
+  gp.seg_bad.assign(C.n_paths, 0);
+  for (size_t i = 0; i < C.n_paths; i++) {
+    try {
+      gp.segs[i] = C.E.get_segment(C.paths[i], true);
+    } catch (const PlanError& e) {
+      if (e.code != LK_ERR_IO) throw;   // capability gaps / evicted keys fail the call (ADVICE r3)
+      gp.seg_bad[i] = 1;
+    }
+  }
+  const std::vector<std::string> proj = qs.tagnum ? std::vector<std::string>{kTimestamp, numtag}
+                                       : qs.logs ? std::vector<std::string>{kTimestamp, kValue, kName, kMessage}
+                                                 : std::vector<std::string>{kTimestamp, kValue, kSpanName, kSpanKind};
+  const std::set<std::string> fset = field_set(R);
+  for (size_t i = 0; i < C.n_paths; i += size_t(C.glob_size)) {
+    XGlob g;
+    for (size_t j = i; j < std::min(C.n_paths, i + size_t(C.glob_size)); j++) g.segs.push_back(int(j));
+    g.win_lo = INT64_MAX;
+    g.win_hi = INT64_MIN;
+    std::vector<std::string> uni;
+    for (int si : g.segs) {
+      g.win_lo = std::min(g.win_lo, R.segments[si].start_ts);
+      g.win_hi = std::max(g.win_hi, R.segments[si].end_ts);
+      if (gp.seg_bad[si]) {
+        g.skip = true;
+        continue;
+      }
+      for (auto& [name, pt] : gp.segs[si]->schema) {
+        if (!g.types.count(name)) uni.push_back(name);
+        // a union this engine does not form (e.g. VARCHAR with a number, which DuckDB unifies to VARCHAR): the call
+        // fails with LK_ERR_UNSUPPORTED so the caller can fall back (ADVICE r3), not an empty glob
+        g.types[name] = union_type(g.type_or(name, -1), pt);
+      }
+    }
+    for (auto& l : fp.leaves)   // nonExistentFields -> literal false (Commons.scala:224, BaseExpr.scala:462-464)
+      if (fset.count(l.node->k) && !g.types.count(l.node->k)) g.leaf_false |= 1u << l.index;
+    for (auto& p : proj)      // Binder Error -> empty glob (Commons.scala:249-253)
+      if (!g.types.count(p)) g.skip = true;
+    for (auto& l : fp.leaves)
+      if (!(g.leaf_false >> l.index & 1u) && !g.types.count(l.node->k)) g.skip = true;
+    for (auto& k : fp.bad_literal)   // normalizedValue failed for a field this glob has
+      if (!(fset.count(k) && !g.types.count(k))) g.skip = true;
+    if (qs.tagnum && g.type_or(numtag, -1) == pq::BYTE_ARRAY)   // VARCHAR in a glob of numbers
+      throw PlanError(LK_ERR_UNSUPPORTED, "tag column " + numtag + " is text in some files and numeric in others");
+    for (auto& nm : qs.nums)   // a VARCHAR compared with a number: Binder Error -> empty glob
+      if (g.type_or(nm, -1) == pq::BYTE_ARRAY) g.skip = true;
+    g.cols = proj;
+    for (auto& u : uni)
+      if (std::find(g.cols.begin(), g.cols.end(), u) == g.cols.end()) g.cols.push_back(u);
+    gp.globs.push_back(std::move(g));
+  }
+  return gp;
+}
+
+// Per filter column: dictionary value -> leaf bits (cached per (column, leaves) like the aggregate path; a pattern
+// RE2 rejects throws out of the call).
+std::vector<std::vector<uint32_t>> x_tables(Engine& E, const XFilter& fp) {
+  std::vector<std::vector<uint32_t>> tabs(fp.strs.size());
+  for (size_t s = 0; s < fp.strs.size(); s++) {
+    GlobalDict& gd = E.dict(fp.strs[s].name);
+    std::lock_guard<std::mutex> dg(gd.mu);
+    const uint32_t dict_n = uint32_t(gd.size());
+    const LockedLeafBits cached = extend_leaf_bits(E, fp.strs[s], gd, dict_n);
+    tabs[s].resize(std::max<uint32_t>(dict_n, 1));
+    for (uint32_t gid = 0; gid < dict_n; gid++) tabs[s][gid] = uint32_t(cached.lb->hit[gid]) << 24;
+  }
+  return tabs;
+}
+
+// Query column qc of q = S's column `name`, when S has it.
+void bind_col(QSeg& q, int qc, const Segment& S, const std::string& name, bool want_string, const XShape& qs,
+              const XFilter& fp, const XGlob& g) {
+  const int c = S.col_index(name);
+  if (c < 0) return;
+  const HostCol& hc = S.cols[c];
+  if (want_string != hc.is_string)
+    throw PlanError(LK_ERR_UNSUPPORTED, "column " + name + " has an unexpected type for its role");
+  if (qc == 0 && hc.ptype != pq::INT64 && hc.ptype != pq::INT32)
+    throw PlanError(LK_ERR_UNSUPPORTED, "timestamp column must be INT64 or INT32");
+  const bool is_tag = qs.tagnum && name == qs.numtag;
+  if (qc >= 2 + int(fp.strs.size()) && hc.ptype != pq::INT64 && hc.ptype != pq::DOUBLE && hc.ptype != pq::INT32 &&
+      hc.ptype != pq::FLOAT && !(is_tag && hc.ptype == pq::BOOLEAN))
+    throw PlanError(LK_ERR_UNSUPPORTED, "numeric comparison on column " + name + " of an undecoded type");
+  uint32_t pad = uint32_t(hc.ptype);
+  if (is_tag) pad |= uint32_t(g.type_or(name, hc.ptype)) << 8;   // the glob's union type
+  q.cols[qc] = QCol{hc.d_pages, hc.d_runs, hc.d_tcols, hc.d_remap, 1u, pad};
+}
+
+// Per-segment descriptors.  A referenced column this engine does not decode fails the call (LK_ERR_UNSUPPORTED: the
+// caller falls back), where a column of a type the query cannot bind is DuckDB's Binder Error: the glob's descriptors
+// go in together or not at all, an empty glob (Commons.scala:249-253) that leaves the other globs unaffected.
+XSegs x_segments(const XShape& qs, const XFilter& fp, XGlobs& gp) {
+  for (const XGlob& g : gp.globs) {
+    if (g.skip) continue;
+    for (int si : g.segs) {
+      if (!gp.segs[si] || gp.segs[si]->unloaded.empty()) continue;
+      const Segment& S = *gp.segs[si];
+      std::vector<std::string> used{kTimestamp};
+      for (auto& sc : fp.strs) used.push_back(sc.name);
+      used.insert(used.end(), qs.nums.begin(), qs.nums.end());
+      used.insert(used.end(), g.cols.begin(), g.cols.end());
+      for (auto& c : used) {
+        const auto u = S.unloaded.find(c);
+        if (u != S.unloaded.end()) throw PlanError(LK_ERR_UNSUPPORTED, u->second + " (" + S.key + ")");
+      }
+    }
+  }
+  XSegs sg;
+  for (size_t gi = 0; gi < gp.globs.size(); gi++) {
+    XGlob& g = gp.globs[gi];
+    if (g.skip || g.win_lo >= g.win_hi || (qs.limit == 0 && !qs.tagnum)) continue;
+    std::vector<QSeg> gq;
+    std::vector<XSegMeta> gm;
+    try {
+      for (size_t p = 0; p < g.segs.size(); p++) {
+        const Segment& S = *gp.segs[g.segs[p]];
+        QSeg q{};
+        q.base = S.d_data;
+        q.tiles = S.d_tiles;
+        q.ntiles = uint32_t(S.tiles.size());
+        q.glob_slot = uint32_t(gi);
+        q.leaf_false = g.leaf_false;
+        q.win_lo = g.win_lo;
+        q.win_hi = g.win_hi;
+        bind_col(q, 0, S, kTimestamp, false, qs, fp, g);
+        if (!q.cols[0].present) continue;
+        for (size_t s = 0; s < fp.strs.size(); s++) bind_col(q, int(2 + s), S, fp.strs[s].name, true, qs, fp, g);
+        for (size_t n = 0; n < qs.nums.size(); n++)
+          bind_col(q, int(2 + fp.strs.size() + n), S, qs.nums[n], false, qs, fp, g);
+        gq.push_back(q);
+        gm.push_back(XSegMeta{&S, uint32_t(p), uint32_t(gi)});
+      }
+    } catch (const PlanError& e) {
+      if (e.code != LK_ERR_UNSUPPORTED) throw;
+      g.skip = true;
+      continue;
+    }
+    g.open = true;
+    sg.qsegs.insert(sg.qsegs.end(), gq.begin(), gq.end());
+    sg.meta.insert(sg.meta.end(), gm.begin(), gm.end());
+  }
+  for (size_t q = 0; q < sg.qsegs.size(); q++) {
+    sg.rows_scanned += uint64_t(sg.meta[q].seg->num_rows);
+    sg.max_tiles = std::max(sg.max_tiles, sg.qsegs[q].ntiles);
+  }
+  if (sg.qsegs.size() > 65535) throw PlanError(LK_ERR_UNSUPPORTED, "more than 65535 segments in one evaluation");
+  return sg;
+}
+
+// Device staging: [segments | truth table | leaf-bit tables | string params | range words | counter], 256-aligned.
+XDev x_stage(const EvalCall& C, const XShape& qs, const XFilter& fp, const std::vector<std::vector<uint32_t>>& tabs,
+             const XSegs& sg, size_t ng) {
+  HIP_TRY(hipSetDevice(C.E.device));
+  XDev D;
+  D.st = C.X.stream;
+  const std::vector<LeafCol>& strs = fp.strs;
+  std::vector<uint32_t> truth;
+  if (fp.leaves.size() <= size_t(TT_MAX_LEAVES)) truth = truth_table(fp.prog, uint32_t(fp.leaves.size()));
+  std::vector<StrParam> strp(strs.size());
+  size_t off = 0;
+  auto reserve = [&](size_t n) { size_t o = (off + 255) / 256 * 256; off = o + n; return o; };
+  const size_t o_segs = reserve(sg.qsegs.size() * sizeof(QSeg));
+  const size_t o_truth = reserve(truth.size() * 4);
+  std::vector<size_t> o_tab(strs.size());
+  for (size_t s = 0; s < strs.size(); s++) o_tab[s] = reserve(tabs[s].size() * 4);
+  const size_t o_strp = reserve(strp.size() * sizeof(StrParam));
+  D.o_rng = reserve(ng * 8 * 4);          // rlo, rhi, hbase, hwidth
+  D.o_n = reserve(8);
+  D.stage_bytes = off;
+  const size_t o_hist = reserve(ng * XBINS * 4);   // host side only
+  uint8_t* hbuf = D.hbuf = static_cast<uint8_t*>(C.X.pinned_buf(off));
+  uint8_t* dbuf = D.dbuf = static_cast<uint8_t*>(C.X.workspace("xquery", D.stage_bytes));
+  D.d_hist = static_cast<uint32_t*>(C.X.workspace("xhist", std::max<size_t>(ng * XBINS * 4, 4)));
+  D.hist = reinterpret_cast<uint32_t*>(hbuf + o_hist);
+  D.rng = XRanges{reinterpret_cast<int64_t*>(hbuf + D.o_rng), ng};
+  memcpy(hbuf + o_segs, sg.qsegs.data(), sg.qsegs.size() * sizeof(QSeg));
+  if (!truth.empty()) memcpy(hbuf + o_truth, truth.data(), truth.size() * 4);
+  for (size_t s = 0; s < strs.size(); s++) {
+    memcpy(hbuf + o_tab[s], tabs[s].data(), tabs[s].size() * 4);
+    strp[s].strtab = reinterpret_cast<const uint32_t*>(dbuf + o_tab[s]);
+    strp[s].lbase = strs[s].lbase;
+    strp[s].lmask = strs[s].lmask;
+    strp[s].hmask = strs[s].hmask;
+  }
+  memcpy(hbuf + o_strp, strp.data(), strp.size() * sizeof(StrParam));
+  XParams& P = D.P;
+  P.segs = reinterpret_cast<const QSeg*>(dbuf + o_segs);
+  P.nsegs = uint32_t(sg.qsegs.size());
+  P.max_tiles = sg.max_tiles;
+  P.strp = reinterpret_cast<const StrParam*>(dbuf + o_strp);
+  P.nstr = uint32_t(strs.size());
+  P.nleaves = uint32_t(fp.leaves.size());
+  P.nprog = uint32_t(fp.prog.size());
+  memcpy(P.prog, fp.prog.data(), fp.prog.size());
+  P.truth = truth.empty() ? nullptr : reinterpret_cast<const uint32_t*>(dbuf + o_truth);
+  P.nnum = uint32_t(qs.nums.size());
+  P.nnl = uint32_t(fp.nleaves.size());
+  for (size_t i = 0; i < fp.nleaves.size(); i++) P.nl[i] = fp.nleaves[i];
+  const XRanges d_rng{reinterpret_cast<int64_t*>(dbuf + D.o_rng), ng};
+  P.rlo = &d_rng.rlo(0);
+  P.rhi = &d_rng.rhi(0);
+  P.hbase = &d_rng.hbase(0);
+  P.hwidth = &d_rng.hwidth(0);
+  P.out_n = reinterpret_cast<uint32_t*>(dbuf + D.o_n);
+  P.tag_qc = ~0u;
+  return D;
+}
+
+// ---- tag query over a numeric tag: SELECT "<tag>", COUNT(*) ... GROUP BY "<tag>" per glob (BaseExpr.scala:127-138):
+// one TAGNUM pass counts passing rows per (glob, canonical tag value); the host prints each value as JDBC getString
+// does for the glob's union_by_name type (Long / Integer / Double / Float / Boolean .toString) ----
+
+struct TagTable {
+  uint64_t tcap = 0;
+  int attempts = 0;
+  uint32_t nrec = 0;
+  std::vector<unsigned long long> hrec;   // [nrec]: key, count, glob
+  std::vector<unsigned long long> spec;   // [ng]: NULL rows, all-ones-key rows
 };
-}  // namespace
 
-namespace {
-// Row streams as bytes (the ranks' exchange): tag names, then per row ts | value | present tags (column, text).
+struct TRow {
+  uint32_t glob;
+  bool null;
+  unsigned long long key;
+  uint64_t count;
+  std::string text;
+};
+
+// The TAGNUM pass, its table regrown while it overflows; then the occupied slots as records.
+TagTable tagnum_scan(const EvalCall& C, const XShape& qs, const XFilter& fp, const XGlobs& gp, const XSegs& sg, XDev& D) {
+  CallCtx& X = C.X;
+  hipStream_t st = D.st;
+  XParams& P = D.P;
+  const size_t ng = gp.globs.size();
+  auto pow2 = [](uint64_t x) {
+    uint64_t p = 1;
+    while (p < x) p <<= 1;
+    return p;
+  };
+  const uint64_t init_slots = pow2(env_u64("LK_TAGNUM_INIT_SLOTS", uint64_t(1) << 12, 64));
+  TagTable T;
+  const uint32_t tagk = uint32_t(std::find(qs.nums.begin(), qs.nums.end(), qs.numtag) - qs.nums.begin());
+  P.tag_qc = uint32_t(2 + fp.strs.size() + tagk);
+  for (size_t gi = 0; gi < ng; gi++) {
+    const XGlob& g = gp.globs[gi];
+    D.rng.range(gi, !g.skip && g.win_lo < g.win_hi, g.win_lo, g.win_hi);
+  }
+  uint64_t max_rows = 1;
+  std::vector<uint64_t> grow(ng, 0);
+  for (const XSegMeta& m : sg.meta) grow[m.glob] += uint64_t(m.seg->num_rows);
+  for (uint64_t r : grow) max_rows = std::max(max_rows, r);
+  const uint64_t cap_max = std::max<uint64_t>(1 << 12, pow2(2 * max_rows));
+  uint64_t tcap = std::min<uint64_t>(cap_max, init_slots);
+  HIP_TRY(hipMemcpyAsync(D.dbuf, D.hbuf, D.stage_bytes, hipMemcpyHostToDevice, st));
+  P.mode = XMODE_TAGNUM;
+  for (;;) {
+    T.attempts++;
+    const size_t tbytes = ng * tcap * 16 + ng * 16 + 64;
+    uint8_t* tb = static_cast<uint8_t*>(X.workspace("tagnum", tbytes));
+    P.tkeys = reinterpret_cast<unsigned long long*>(tb);
+    P.tcnt = reinterpret_cast<unsigned long long*>(tb + ng * tcap * 8);
+    P.tspec = reinterpret_cast<unsigned long long*>(tb + ng * tcap * 16);
+    P.tflags = reinterpret_cast<uint32_t*>(tb + ng * tcap * 16 + ng * 16);
+    P.tcap = tcap;
+    HIP_TRY(hipMemsetAsync(tb, 0xff, ng * tcap * 8, st));
+    HIP_TRY(hipMemsetAsync(tb + ng * tcap * 8, 0, ng * tcap * 8 + ng * 16 + 64, st));
+    D.scan(X);
+    uint32_t fl = 0;
+    HIP_TRY(hipMemcpyAsync(&fl, P.tflags, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    D.scanned(X);
+    if (!(fl & FLAG_HASH_FULL)) break;
+    if (tcap >= cap_max) throw PlanError(LK_ERR_MEMORY, "tag value table full at its bound");
+    tcap = std::min(cap_max, tcap * 8);
+  }
+  T.tcap = tcap;
+  // occupied slots -> (key, count, glob) records; per-glob NULL / all-ones counts
+  auto* recs = static_cast<unsigned long long*>(X.workspace("tagrecs", ng * tcap * 24 + 64));
+  uint32_t* d_n = reinterpret_cast<uint32_t*>(recs);
+  HIP_TRY(hipMemsetAsync(d_n, 0, 4, st));
+  HIP_TRY(launch_tag_compact(P.tkeys, P.tcnt, tcap, uint32_t(ng), recs + 1, d_n, st));
+  T.spec.resize(ng * 2);
+  HIP_TRY(hipMemcpyAsync(&T.nrec, d_n, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(T.spec.data(), P.tspec, ng * 16, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  T.hrec.resize(size_t(T.nrec) * 3);
+  if (T.nrec) {
+    HIP_TRY(hipMemcpyAsync(T.hrec.data(), recs + 1, size_t(T.nrec) * 24, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  return T;
+}
+
+// Per glob: (key, count) in the union type's value order, NULL last; merged: counts summed per tag text (NULL apart).
+std::vector<TRow> tagnum_rows(const XShape& qs, const XGlobs& gp, const TagTable& T) {
+  const size_t ng = gp.globs.size();
+  std::vector<int> ut(ng);   // the tag's union type per glob
+  for (size_t gi = 0; gi < ng; gi++) ut[gi] = gp.globs[gi].type_or(qs.numtag, pq::INT64);
+  std::vector<TRow> rows;
+  for (uint32_t i = 0; i < T.nrec; i++)
+    rows.push_back(TRow{uint32_t(T.hrec[3 * i + 2]), false, T.hrec[3 * i], T.hrec[3 * i + 1], std::string()});
+  for (uint32_t gi = 0; gi < ng; gi++) {
+    if (T.spec[2 * gi + 1]) rows.push_back(TRow{gi, false, TAG_EMPTY, T.spec[2 * gi + 1], std::string()});
+    if (T.spec[2 * gi]) rows.push_back(TRow{gi, true, 0, T.spec[2 * gi], std::string()});
+  }
+  for (auto& r : rows)
+    if (!r.null) r.text = value_text(r.key, ut[r.glob], ut[r.glob]);
+  std::sort(rows.begin(), rows.end(), [&](const TRow& a, const TRow& b) {
+    if (a.glob != b.glob) return a.glob < b.glob;
+    if (a.null != b.null) return b.null;
+    if (a.null) return false;
+    const int t = ut[a.glob];
+    if (t != pq::DOUBLE && t != pq::FLOAT)       // integers (the all-ones key is -1): exact order, not as doubles
+      return int64_t(a.key) < int64_t(b.key);    // (beyond 2^53 doubles tie and the text order is wrong)
+    const double x = raw_as_double(a.key, t), y = raw_as_double(b.key, t);
+    if (x != y && x == x && y == y) return x < y;
+    return a.text < b.text;
+  });
+  if (!qs.per_glob_rows) {
+    rows = sum_first_seen(
+        rows, [](const TRow& r) { return std::make_pair(r.null, r.text); },
+        [](TRow& kept, const TRow& r) { kept.count += r.count; });
+    for (auto& r : rows) r.glob = 0;
+  }
+  return rows;
+}
+
+// Rows: Commons.toDataPoint's tag branch (Commons.scala:406-423): the tag (dropped when NULL / "" / "null" or a noisy
+// name, NoisyTagsDropper) and "count"; value = the count, timestamp = now (as the string tag path).
+void tagnum_result(const EvalCall& C, const XShape& qs, const XGlobs& gp, const XSegs& sg, const XDev& D,
+                   const TagTable& T, const std::vector<TRow>& rows) {
+  lk_result* res = C.res;
+  const int64_t now_ms = std::chrono::duration_cast<std::chrono::milliseconds>(
+                             std::chrono::system_clock::now().time_since_epoch()).count();
+  const bool hide = noisy_tag(qs.numtag);
+  res->per_glob = qs.per_glob_rows;
+  res->alloc_rows(rows.size());
+  res->tag_names = {qs.numtag, "count"};
+  res->ex_tags.assign(rows.size() * 2, nullptr);
+  for (size_t i = 0; i < rows.size(); i++) {
+    res->ts[i] = now_ms;
+    res->val[i] = double(rows[i].count);
+    res->glob[i] = rows[i].glob;
+    res->gid[i] = uint32_t(i);
+    if (!rows[i].null && !hide && !null_like(rows[i].text)) {
+      res->owned.push_back(rows[i].text);
+      res->ex_tags[2 * i] = res->owned.back().c_str();
+    }
+    res->owned.push_back(std::to_string((unsigned long long)rows[i].count));
+    res->ex_tags[2 * i + 1] = res->owned.back().c_str();
+  }
+  char buf[320];
+  snprintf(buf, sizeof buf,
+           "{\"scan_ms\":%.4f,\"total_ms\":%.4f,\"rows_scanned\":%llu,\"tag_values\":%u,\"attempts\":%d,"
+           "\"slots\":%llu,\"table\":\"tagnum\",\"failed_globs\":%zu}",
+           double(D.scan_ms), ms_since(C.t_start), (unsigned long long)sg.rows_scanned, T.nrec, T.attempts,
+           (unsigned long long)T.tcap,
+           size_t(std::count_if(gp.globs.begin(), gp.globs.end(), [](const XGlob& g) { return g.skip; })));
+  res->stats = buf;
+}
+
+// ---- exemplar rows ----
+
+// HIST passes: narrow every open glob to the rows that can make its top `limit` (ex_select.hpp); returns the passes.
+int select(const EvalCall& C, const XShape& qs, XGlobs& gp, const XSegs& sg, XDev& D) {
+  // rows listed beyond each glob's `limit` at most, unless tied on one millisecond; rows a zone-map probe covers first
+  // (tests shrink them with LK_EX_CAND_CAP / LK_EX_PROBE_ROWS to exercise the refinement and the probes)
+  const uint64_t cand_cap = env_u64("LK_EX_CAND_CAP", uint64_t(1) << 24, 1);
+  const uint64_t probe_rows = env_u64("LK_EX_PROBE_ROWS", uint64_t(1) << 20, 1);
+  std::vector<XGlob>& globs = gp.globs;
+  const size_t ng = globs.size();
+  hipStream_t st = D.st;
+  std::vector<std::vector<XTile>> zones(ng);
+  for (const XSegMeta& m : sg.meta)
+    for (const TileDesc& td : m.seg->tiles) zones[m.glob].push_back(XTile{td.ts_min, td.ts_max, td.nrows});
+  for (size_t gi = 0; gi < ng; gi++) {
+    XGlob& g = globs[gi];
+    g.start(qs.limit);
+    if (g.open) g.probes = probe_boundaries(zones[gi], g.win_lo, g.win_hi, qs.desc, probe_rows);
+  }
+  int passes = 0;
+  bool first_upload = true;   // the whole staged block once, the range words alone afterwards
+  std::vector<XPass> pass(ng);
+  while (std::any_of(globs.begin(), globs.end(), [](const XGlob& g) { return g.open; })) {
+    for (size_t gi = 0; gi < ng; gi++) {
+      const XPass& p = pass[gi] = next_pass(globs[gi], qs.desc, XBINS);
+      D.rng.rlo(gi) = p.rlo;
+      D.rng.rhi(gi) = p.rhi;
+      D.rng.hbase(gi) = p.hbase;
+      D.rng.hwidth(gi) = p.hwidth;
+    }
+    HIP_TRY(hipMemcpyAsync(first_upload ? D.dbuf : D.dbuf + D.o_rng, first_upload ? D.hbuf : D.hbuf + D.o_rng,
+                            first_upload ? D.stage_bytes : ng * 32, hipMemcpyHostToDevice, st));
+    first_upload = false;
+    HIP_TRY(hipMemsetAsync(D.d_hist, 0, ng * XBINS * 4, st));
+    D.P.mode = XMODE_HIST;
+    D.P.nbins = XBINS;
+    D.P.hist = D.d_hist;
+    D.scan(C.X);
+    HIP_TRY(hipMemcpyAsync(D.hist, D.d_hist, ng * XBINS * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    D.scanned(C.X);
+    passes++;
+    for (size_t gi = 0; gi < ng; gi++)
+      if (globs[gi].open) narrow(globs[gi], D.hist + gi * XBINS, pass[gi].nb, pass[gi].hwidth, qs.desc, cand_cap);
+  }
+  return passes;
+}
+
+// EMIT: the `total` candidates of every glob's final range.
+std::vector<Cand> emit_candidates(const EvalCall& C, const XGlobs& gp, const XSegs& sg, XDev& D, uint64_t total) {
+  if (total > (uint64_t(1) << 28)) throw PlanError(LK_ERR_UNSUPPORTED, "too many exemplar candidates");
+  std::vector<Cand> cands;
+  if (!total) return cands;
+  const size_t ng = gp.globs.size();
+  hipStream_t st = D.st;
+  for (size_t gi = 0; gi < ng; gi++) D.rng.range(gi, gp.globs[gi].count > 0, gp.globs[gi].elo, gp.globs[gi].ehi);
+  unsigned long long* d_out = static_cast<unsigned long long*>(C.X.workspace("xcand", total * 16));
+  HIP_TRY(hipMemcpyAsync(D.dbuf + D.o_rng, D.hbuf + D.o_rng, ng * 16, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(D.dbuf + D.o_n, 0, 8, st));
+  D.P.mode = XMODE_EMIT;
+  D.P.out = d_out;
+  D.P.cap = uint32_t(total);
+  D.scan(C.X);
+  // pinned destinations: a device-to-host copy into pageable memory goes through the runtime's staging buffers
+  PinnedTmp eo(total * 16 + 64);
+  const unsigned long long* h_out = static_cast<const unsigned long long*>(eo.p());
+  HIP_TRY(hipMemcpyAsync(eo.p(), d_out, total * 16, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(eo.p()) + total * 16, D.dbuf + D.o_n, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint32_t got = 0;
+  memcpy(&got, static_cast<const uint8_t*>(eo.p()) + total * 16, 4);
+  D.scanned(C.X);
+  if (got != total) throw PlanError(LK_ERR_DEVICE, "internal: exemplar candidate count disagrees with the histogram");
+  cands.resize(total);
+  for (uint64_t i = 0; i < total; i++) {
+    const unsigned long long ref = h_out[2 * i + 1];
+    const uint32_t qs = uint32_t(ref >> 48), tile = uint32_t((ref >> 16) & 0xffffffffu), r = uint32_t(ref & 0xffffu);
+    const Segment& S = *sg.meta[qs].seg;
+    const TileDesc& td = S.tiles[tile];
+    uint64_t row = uint64_t(td.row0) + r;
+    for (uint32_t k = 0; k < td.rg; k++) row += uint64_t(S.rg_rows[k]);
+    cands[i] = Cand{int64_t(h_out[2 * i]), qs, sg.meta[qs].pos, row, ref};
+  }
+  return cands;
+}
+
+// Per glob the top `limit` in ORDER BY order (ties: file order), then the Akka mergeSorted fold over the globs' streams
+// (Commons.scala:391-392): merge(merge(merge([], g0), g1), g2)...
+std::vector<const Cand*> order_and_fold(const EvalCall& C, const XShape& qs, size_t ng, const XSegs& sg,
+                                        const std::vector<Cand>& cands) {
+  std::vector<std::vector<const Cand*>> per(ng);
+  for (auto& c : cands) per[sg.meta[c.qseg].glob].push_back(&c);
+  const bool rev = C.R.reverse_sort;   // rollupAgg is empty for exemplars (Commons.scala:125-129)
+  std::vector<const Cand*> stream;
+  for (auto& v : per) {
+    std::sort(v.begin(), v.end(), [&](const Cand* a, const Cand* b) {
+      if (a->ts != b->ts) return qs.desc ? a->ts > b->ts : a->ts < b->ts;
+      if (a->pos != b->pos) return a->pos < b->pos;
+      return a->row < b->row;
+    });
+    if (v.size() > qs.limit) v.resize(size_t(qs.limit));
+    stream = merge_sorted(stream, v, [&](const Cand* a, const Cand* b) { return rev ? a->ts > b->ts : a->ts < b->ts; });
+  }
+  return stream;
+}
+
+// Every output column of the selected rows: raw values [nsel][ncols] and their non-NULL flags.
+struct XGathered {
+  std::vector<std::string> out_cols;
+  std::vector<unsigned long long> val;
+  std::vector<uint8_t> ok;
+};
+XGathered gather_columns(const EvalCall& C, const XGlobs& gp, const XSegs& sg, hipStream_t st,
+                         const std::vector<const Cand*>& stream) {
+  XGathered G;
+  std::vector<std::string>& out_cols = G.out_cols;
+  for (auto& g : gp.globs) {
+    if (g.skip) continue;
+    for (auto& c : g.cols)
+      if (std::find(out_cols.begin(), out_cols.end(), c) == out_cols.end()) out_cols.push_back(c);
+  }
+  const size_t nsel = stream.size(), ncols = out_cols.size(), nq = sg.qsegs.size();
+  G.val.resize(nsel * ncols);
+  G.ok.resize(nsel * ncols);
+  if (!nsel || !ncols) return G;
+  std::vector<GCol> gcols(nq * ncols);
+  for (size_t q = 0; q < nq; q++) {
+    const Segment& S = *sg.meta[q].seg;
+    for (size_t k = 0; k < ncols; k++) {
+      const int c = S.col_index(out_cols[k]);
+      if (c < 0) {
+        if (S.all_columns.count(out_cols[k]))
+          throw PlanError(LK_ERR_UNSUPPORTED, "column " + out_cols[k] + " has a physical type the engine does not load");
+        continue;
+      }
+      const HostCol& hc = S.cols[c];
+      gcols[q * ncols + k] = GCol{S.d_data, hc.d_runs, hc.d_tcols, hc.d_remap, 1u, 0u};
+    }
+  }
+  const size_t gb = gcols.size() * sizeof(GCol), sb = nsel * 8, vb = nsel * ncols * 8, ob = nsel * ncols;
+  PinnedTmp gio(gb + sb + vb + ob + 64);   // pinned staging both ways: [columns | selected refs | values | ok]
+  uint8_t* hg = static_cast<uint8_t*>(gio.p());
+  memcpy(hg, gcols.data(), gb);
+  for (size_t i = 0; i < nsel; i++) reinterpret_cast<unsigned long long*>(hg + gb)[i] = stream[i]->ref;
+  uint8_t* dg = static_cast<uint8_t*>(C.X.workspace("xgather", gb + sb + vb + ob + 1024));
+  HIP_TRY(hipMemcpyAsync(dg, hg, gb + sb, hipMemcpyHostToDevice, st));
+  GParams P{};
+  P.cols = reinterpret_cast<const GCol*>(dg);
+  P.sel = reinterpret_cast<const unsigned long long*>(dg + gb);
+  P.nsel = uint32_t(nsel);
+  P.ncols = uint32_t(ncols);
+  P.val = reinterpret_cast<unsigned long long*>(dg + gb + sb);
+  P.ok = dg + gb + sb + vb;
+  HIP_TRY(launch_ex_gather(P, st));
+  HIP_TRY(hipMemcpyAsync(hg + gb + sb, P.val, vb + ob, hipMemcpyDeviceToHost, st));   // values and ok flags
+  HIP_TRY(hipStreamSynchronize(st));
+  memcpy(G.val.data(), hg + gb + sb, vb);
+  memcpy(G.ok.data(), hg + gb + sb + vb, ob);
+  return G;
+}
+
+// Rows: timestamp, getDouble(value) (SQL NULL -> 0.0), tags as JDBC getString text.
+void write_rows(const EvalCall& C, const XGlobs& gp, const XSegs& sg, const std::vector<const Cand*>& stream,
+                const XGathered& G) {
+  lk_result* res = C.res;
+  const std::vector<std::string>& out_cols = G.out_cols;
+  const size_t nsel = stream.size(), ncols = out_cols.size(), nq = sg.qsegs.size();
+  res->alloc_rows(nsel);
+  res->tag_names = out_cols;
+  res->ex_tags.assign(nsel * ncols, nullptr);
+  const size_t vcol = size_t(std::find(out_cols.begin(), out_cols.end(), std::string(kValue)) - out_cols.begin());
+  for (size_t i = 0; i < nsel; i++) {
+    res->ts[i] = stream[i]->ts;
+    res->glob[i] = sg.meta[stream[i]->qseg].glob;
+    res->gid[i] = uint32_t(i);
+    res->val[i] = 0.0;
+  }
+  // column by column: each (segment, column)'s physical / union type looked up once, each dictionary locked once
+  std::vector<const HostCol*> qcol(nq);
+  std::vector<int> qut(nq);
+  for (size_t k = 0; k < ncols; k++) {
+    const std::string& name = out_cols[k];
+    bool any_string = false;
+    for (size_t q = 0; q < nq; q++) {
+      const Segment& S = *sg.meta[q].seg;
+      const int ci = S.col_index(name);
+      qcol[q] = ci < 0 ? nullptr : &S.cols[size_t(ci)];
+      if (!qcol[q]) continue;
+      qut[q] = gp.globs[sg.meta[q].glob].type_or(name, qcol[q]->ptype);
+      any_string = any_string || qcol[q]->is_string;
+    }
+    GlobalDict* gd = any_string ? &C.E.dict(name) : nullptr;
+    std::unique_lock<std::mutex> dl;
+    if (gd) {
+      dl = std::unique_lock<std::mutex>(gd->mu);
+      res->keep.push_back(gd->vals);   // tag text outlives a compaction
+    }
+    for (size_t i = 0; i < nsel; i++) {
+      if (!G.ok[i * ncols + k]) continue;
+      const uint32_t q = stream[i]->qseg;
+      const HostCol& hc = *qcol[q];
+      const unsigned long long raw = G.val[i * ncols + k];
+      if (k == vcol) res->val[i] = raw_as_double(raw, hc.ptype);
+      if (hc.is_string) {
+        if (qut[q] != pq::BYTE_ARRAY) throw PlanError(LK_ERR_UNSUPPORTED, "union_by_name over string and numeric " + name);
+        const std::string& s = (*gd)[size_t(raw)];
+        if (!null_like(s)) res->ex_tags[i * ncols + k] = s.c_str();   // Commons.scala:433
+      } else {
+        res->owned.push_back(value_text(raw, hc.ptype, qut[q]));
+        res->ex_tags[i * ncols + k] = res->owned.back().c_str();
+      }
+    }
+  }
+}
+
+// This process's segments; the time in ex_scan goes to *scan_ms too (the distributed call's stats).
+void exemplar_local(const EvalCall& C, const std::string& numtag, double* scan_ms) {
+  lk_result* res = C.res;
+  const XShape qs = x_gate(C, numtag);
+  res->exemplar = true;
+  res->per_glob = true;
+  if (C.R.segments.empty()) return sentinel_row(C, qs);
+  const XFilter fp = x_filter(C, qs);
+  XGlobs gp = x_globs(C, qs, fp);
+  const std::vector<std::vector<uint32_t>> tabs = x_tables(C.E, fp);
+  const XSegs sg = x_segments(qs, fp, gp);
+  XDev D = x_stage(C, qs, fp, tabs, sg, gp.globs.size());
+  if (qs.tagnum) {
+    const TagTable T = tagnum_scan(C, qs, fp, gp, sg, D);
+    tagnum_result(C, qs, gp, sg, D, T, tagnum_rows(qs, gp, T));
+    *scan_ms = double(D.scan_ms);
+    return;
+  }
+  const int passes = select(C, qs, gp, sg, D);
+  uint64_t total = 0;
+  for (auto& g : gp.globs) total += g.count;
+  const std::vector<Cand> cands = emit_candidates(C, gp, sg, D, total);
+  const std::vector<const Cand*> stream = order_and_fold(C, qs, gp.globs.size(), sg, cands);
+  write_rows(C, gp, sg, stream, gather_columns(C, gp, sg, D.st, stream));
+  char buf[256];
+  snprintf(buf, sizeof buf,
+           "{\"scan_ms\":%.4f,\"total_ms\":%.4f,\"rows_scanned\":%llu,\"candidates\":%llu,\"hist_passes\":%d}",
+           double(D.scan_ms), ms_since(C.t_start), (unsigned long long)sg.rows_scanned, (unsigned long long)total, passes);
+  res->stats = buf;
+  *scan_ms = double(D.scan_ms);
+}
+
+// ---- the ranks' exchange ----
+
+// Row streams as bytes: tag names, then per row ts | value | present tags (column, text).
 void put_u32(std::string& b, uint32_t x) { b.append(reinterpret_cast<const char*>(&x), 4); }
 void put_str(std::string& b, const std::string& s) {
   put_u32(b, uint32_t(s.size()));
@@ -185,139 +965,89 @@ struct XRow {
   double val;
   std::vector<std::pair<std::string, std::string>> tags;   // (column name, text), the row's present tags
 };
-}  // namespace
 
-// Distributed exemplar / numeric-tag query (VERDICT r4 missing #1-2).  Reference: query-api fans the pushdown out to
-// every worker pod holding segments of the group (SegmentSequencer.allSources), each pod evaluates its own segments
-// (globs of its own request, Commons.scala:361-392), and query-api merges the pods' streams -- exemplars:
-// flatMapMerge then take(limit) (QueryEngineV2.scala:493-535); tag queries: every pod's (tag, count) rows
-// (QueryEngineV2.scala:452-487).  Here each rank is a pod: it evaluates the segments of its shard as the worker
-// would (its exemplar stream: per-glob top `limit`, globs folded by mergeSorted; its numeric tag rows: counts per tag
-// text over its globs), one all-gather carries every rank's rows (and status: a rank-local failure fails every
-// rank), and rank 0 folds them -- exemplars: Akka mergeSorted over the ranks in rank order (the deterministic
-// stand-in for flatMapMerge's arrival order) and take(limit); numeric tags: counts summed per tag text (NULL apart),
-// in first-seen order, as the string tag query's merged table does.  Other ranks return no rows.
-static int exemplar_dist(Engine& E, CallCtx& X, const Request& R, const char* const* paths, size_t n_paths,
-                         int glob_size, lk_result* res, const std::string& numtag, const int32_t* shard) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const bool tagnum = !numtag.empty();
-  const int world = comm_world(E), rank = comm_rank(E);
-  Request sub = copy_request(R);
-  sub.segments.clear();
-  std::vector<const char*> sp;
-  for (size_t i = 0; i < n_paths; i++)
-    if ((shard ? shard[i] : int32_t(i % size_t(world))) == rank) {
-      sp.push_back(paths[i]);
-      sub.segments.push_back(R.segments[i]);
-    }
-  int code = 0;
-  std::string msg, blob;
-  double scan_ms = 0;
-  uint64_t local_rows = 0;
-  if (!sp.empty()) {   // a pod with no segment of the group is not asked at all (no sentinel row)
-    try {
-      lk_result local;
-      evaluate_exemplar(E, X, sub, sp.data(), sp.size(), glob_size, tagnum ? LK_MERGED : LK_PER_GLOB_ROWS, false,
-                        &local, numtag);
-      const size_t nt = local.tag_names.size();
-      put_u32(blob, uint32_t(nt));
-      for (auto& n : local.tag_names) put_str(blob, n);
-      const uint64_t n = local.nrows;
-      blob.append(reinterpret_cast<const char*>(&n), 8);
-      for (size_t i = 0; i < local.nrows; i++) {
-        blob.append(reinterpret_cast<const char*>(&local.ts[i]), 8);
-        blob.append(reinterpret_cast<const char*>(&local.val[i]), 8);
-        uint32_t present = 0;
-        for (size_t c = 0; c < nt; c++) present += local.tag(i, c) != nullptr;
-        put_u32(blob, present);
-        for (size_t c = 0; c < nt; c++)
-          if (const char* v = local.tag(i, c)) {
-            put_u32(blob, uint32_t(c));
-            put_str(blob, v);
-          }
+std::string encode_rows(const lk_result& local) {
+  std::string blob;
+  const size_t nt = local.tag_names.size();
+  put_u32(blob, uint32_t(nt));
+  for (auto& n : local.tag_names) put_str(blob, n);
+  const uint64_t n = local.nrows;
+  blob.append(reinterpret_cast<const char*>(&n), 8);
+  for (size_t i = 0; i < local.nrows; i++) {
+    blob.append(reinterpret_cast<const char*>(&local.ts[i]), 8);
+    blob.append(reinterpret_cast<const char*>(&local.val[i]), 8);
+    uint32_t present = 0;
+    for (size_t c = 0; c < nt; c++) present += local.tag(i, c) != nullptr;
+    put_u32(blob, present);
+    for (size_t c = 0; c < nt; c++)
+      if (const char* v = local.tag(i, c)) {
+        put_u32(blob, uint32_t(c));
+        put_str(blob, v);
       }
-      local_rows = local.nrows;
-      const char* k = strstr(local.stats.c_str(), "\"scan_ms\":");
-      if (k) scan_ms = atof(k + 10);
-    } catch (const PlanError& e) {
-      code = e.code;
-      msg = e.what();
-    } catch (const std::exception& e) {
-      code = LK_ERR_DEVICE;
-      msg = e.what();
+  }
+  return blob;
+}
+
+// The ranks' streams; `names`: their tag columns in first-seen order over the ranks.
+std::vector<std::vector<XRow>> decode_rows(const std::vector<std::string>& all, std::vector<std::string>& names) {
+  std::vector<std::vector<XRow>> streams(all.size());
+  for (size_t r = 0; r < all.size(); r++) {
+    if (all[r].empty()) continue;
+    Reader rd{all[r]};
+    const uint32_t nt = rd.get<uint32_t>();
+    std::vector<std::string> tn(nt);
+    for (auto& t : tn) t = rd.str();
+    for (auto& t : tn)
+      if (std::find(names.begin(), names.end(), t) == names.end()) names.push_back(t);
+    const uint64_t n = rd.get<uint64_t>();
+    streams[r].resize(size_t(n));
+    for (auto& row : streams[r]) {
+      row.ts = rd.get<int64_t>();
+      row.val = rd.get<double>();
+      const uint32_t np = rd.get<uint32_t>();
+      for (uint32_t j = 0; j < np; j++) {
+        const uint32_t c = rd.get<uint32_t>();
+        if (c >= nt) throw PlanError(LK_ERR_DEVICE, "internal: bad tag column in a rank's exemplar stream");
+        row.tags.emplace_back(tn[c], rd.str());
+      }
     }
   }
-  const std::vector<std::string> all = comm_allgather_status(E, X, code, msg, blob);
-  res->exemplar = true;
-  res->per_glob = false;
+  return streams;
+}
+
+// Rank 0's fold.  Exemplars: Akka mergeSorted over the ranks' streams in rank order, then take(limit).  Numeric tags:
+// counts summed per tag text (the "count" tag rewritten), NULL / dropped tag apart, first-seen order.
+// A deliberate deviation: query-api's streamTags (QueryEngineV2.scala:452-487) flatMapMerges the
+// pods' (tag, count) rows unsummed, in arrival order (TagQueryUtils.aggregate is commented out there), so a
+// value present on two pods reaches the client twice.  The distributed call returns one merged table instead
+// -- the same table the string-tag distributed path returns (one row per value, counts added) -- because
+// arrival order across ranks is not reproducible; DESIGN.md §5 records this.
+std::vector<XRow> fold_ranks(const Request& R, const std::string& numtag, std::vector<std::vector<XRow>>& streams) {
   std::vector<XRow> out;
-  std::vector<std::string> names;   // tag columns, first-seen order over the ranks
-  if (rank == 0) {
-    std::vector<std::vector<XRow>> streams(all.size());
-    for (size_t r = 0; r < all.size(); r++) {
-      if (all[r].empty()) continue;
-      Reader rd{all[r]};
-      const uint32_t nt = rd.get<uint32_t>();
-      std::vector<std::string> tn(nt);
-      for (auto& t : tn) t = rd.str();
-      for (auto& t : tn)
-        if (std::find(names.begin(), names.end(), t) == names.end()) names.push_back(t);
-      const uint64_t n = rd.get<uint64_t>();
-      streams[r].resize(size_t(n));
-      for (auto& row : streams[r]) {
-        row.ts = rd.get<int64_t>();
-        row.val = rd.get<double>();
-        const uint32_t np = rd.get<uint32_t>();
-        for (uint32_t j = 0; j < np; j++) {
-          const uint32_t c = rd.get<uint32_t>();
-          if (c >= nt) throw PlanError(LK_ERR_DEVICE, "internal: bad tag column in a rank's exemplar stream");
-          row.tags.emplace_back(tn[c], rd.str());
-        }
-      }
-    }
-    if (!tagnum) {
-      // Akka mergeSorted fold over the ranks' streams (left head when strictly less), then take(limit)
-      const bool rev = R.reverse_sort;
-      for (auto& v : streams) {
-        std::vector<XRow> m;
-        m.reserve(out.size() + v.size());
-        size_t i = 0, j = 0;
-        while (i < out.size() && j < v.size()) {
-          const bool lt = rev ? out[i].ts > v[j].ts : out[i].ts < v[j].ts;
-          if (lt) m.push_back(std::move(out[i++]));
-          else m.push_back(std::move(v[j++]));
-        }
-        while (i < out.size()) m.push_back(std::move(out[i++]));
-        while (j < v.size()) m.push_back(std::move(v[j++]));
-        out.swap(m);
-      }
-      if (R.limit >= 0 && out.size() > uint64_t(R.limit)) out.resize(size_t(R.limit));
-    } else {
-      // counts summed per tag text (the "count" tag rewritten), NULL / dropped tag apart, first-seen order.
-      // A deliberate deviation: query-api's streamTags (QueryEngineV2.scala:452-487) flatMapMerges the
-      // pods' (tag, count) rows unsummed, in arrival order (TagQueryUtils.aggregate is commented out there), so a
-      // value present on two pods reaches the client twice.  The distributed call returns one merged table instead
-      // -- the same table the string-tag distributed path returns (one row per value, counts added) -- because
-      // arrival order across ranks is not reproducible; DESIGN.md §5 records this.
-      std::map<std::string, size_t> at;
-      for (auto& v : streams)
-        for (auto& row : v) {
-          std::string key = "\x01";   // the tag dropped (NULL or a null-like text)
-          for (auto& kv : row.tags)
-            if (kv.first == numtag) key = "\x02" + kv.second;
-          auto it = at.find(key);
-          if (it == at.end()) {
-            at.emplace(key, out.size());
-            out.push_back(std::move(row));
-          } else {
-            out[it->second].val += row.val;
-          }
-        }
-      for (auto& row : out)
-        for (auto& kv : row.tags)
-          if (kv.first == "count") kv.second = std::to_string((unsigned long long)row.val);
-    }
+  if (numtag.empty()) {
+    const bool rev = R.reverse_sort;
+    for (auto& v : streams)
+      out = merge_sorted(out, v, [&](const XRow& a, const XRow& b) { return rev ? a.ts > b.ts : a.ts < b.ts; });
+    if (R.limit >= 0 && out.size() > uint64_t(R.limit)) out.resize(size_t(R.limit));
+    return out;
   }
+  for (auto& v : streams) std::move(v.begin(), v.end(), std::back_inserter(out));
+  out = sum_first_seen(
+      out,
+      [&](const XRow& row) {
+        std::string key = "\x01";   // the tag dropped (NULL or a null-like text)
+        for (auto& kv : row.tags)
+          if (kv.first == numtag) key = "\x02" + kv.second;
+        return key;
+      },
+      [](XRow& kept, const XRow& row) { kept.val += row.val; });
+  for (auto& row : out)
+    for (auto& kv : row.tags)
+      if (kv.first == "count") kv.second = std::to_string((unsigned long long)row.val);
+  return out;
+}
+
+void write_dist_rows(lk_result* res, const std::vector<XRow>& out, const std::vector<std::string>& names) {
   res->alloc_rows(out.size());
   res->tag_names = names;
   res->ex_tags.assign(out.size() * names.size(), nullptr);
@@ -332,778 +1062,78 @@ static int exemplar_dist(Engine& E, CallCtx& X, const Request& R, const char* co
       res->ex_tags[i * names.size() + c] = res->owned.back().c_str();
     }
   }
+}
+
+// Distributed exemplar / numeric-tag query (VERDICT r4 missing #1-2).  Reference: query-api fans the pushdown out to
+// every worker pod holding segments of the group (SegmentSequencer.allSources), each pod evaluates its own segments
+// (globs of its own request, Commons.scala:361-392), and query-api merges the pods' streams -- exemplars:
+// flatMapMerge then take(limit) (QueryEngineV2.scala:493-535); tag queries: every pod's (tag, count) rows
+// (QueryEngineV2.scala:452-487).  Here each rank is a pod: it evaluates the segments of its shard as the worker
+// would (its exemplar stream: per-glob top `limit`, globs folded by mergeSorted; its numeric tag rows: counts per tag
+// text over its globs), one all-gather carries every rank's rows (and status: a rank-local failure fails every
+// rank), and rank 0 folds them (fold_ranks; rank order is the deterministic stand-in for flatMapMerge's arrival
+// order).  Other ranks return no rows.
+void exemplar_dist(const EvalCall& C, const std::string& numtag) {
+  const Request& R = C.R;
+  const int32_t* shard = C.shard;
+  const bool tagnum = !numtag.empty();
+  const int world = comm_world(C.E), rank = comm_rank(C.E);
+  Request sub = copy_request(R);
+  sub.segments.clear();
+  std::vector<const char*> sp;
+  for (size_t i = 0; i < C.n_paths; i++)
+    if ((shard ? shard[i] : int32_t(i % size_t(world))) == rank) {
+      sp.push_back(C.paths[i]);
+      sub.segments.push_back(R.segments[i]);
+    }
+  int code = 0;
+  std::string msg, blob;
+  double scan_ms = 0;
+  uint64_t local_rows = 0;
+  if (!sp.empty()) {   // a pod with no segment of the group is not asked at all (no sentinel row)
+    try {
+      lk_result local;
+      const unsigned flags = tagnum ? LK_MERGED : LK_PER_GLOB_ROWS;
+      exemplar_local(EvalCall{C.E, C.X, sub, sp.data(), sp.size(), C.glob_size, flags, nullptr, false, 0, &local,
+                              std::chrono::steady_clock::now()}, numtag, &scan_ms);
+      blob = encode_rows(local);
+      local_rows = local.nrows;
+    } catch (const PlanError& e) {
+      code = e.code;
+      msg = e.what();
+    } catch (const std::exception& e) {
+      code = LK_ERR_DEVICE;
+      msg = e.what();
+    }
+  }
+  const std::vector<std::string> all = comm_allgather_status(C.E, C.X, code, msg, blob);
+  C.res->exemplar = true;
+  C.res->per_glob = false;
+  std::vector<XRow> out;
+  std::vector<std::string> names;
+  if (rank == 0) {
+    std::vector<std::vector<XRow>> streams = decode_rows(all, names);
+    out = fold_ranks(R, numtag, streams);
+  }
+  write_dist_rows(C.res, out, names);
   char buf[320];
   snprintf(buf, sizeof buf,
            "{\"scan_ms\":%.4f,\"total_ms\":%.4f,\"rank_rows\":%llu,\"rows\":%zu,\"reduce\":\"%s\",\"table\":\"%s\"}",
-           scan_ms, ms_since(t0), (unsigned long long)local_rows, out.size(), tagnum ? "tag_counts" : "merge_sorted",
-           tagnum ? "tagnum" : "exemplar");
-  res->stats = buf;
-  return LK_OK;
+           scan_ms, ms_since(C.t_start), (unsigned long long)local_rows, out.size(),
+           tagnum ? "tag_counts" : "merge_sorted", tagnum ? "tagnum" : "exemplar");
+  C.res->stats = buf;
 }
+
+}  // namespace
 
 int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const* paths, size_t n_paths,
                       int glob_size, unsigned flags, bool dist, lk_result* res, const std::string& numtag,
                       const int32_t* shard) {
-  const auto t_start = std::chrono::steady_clock::now();
-  const bool tagnum = !numtag.empty();
-  if (dist) return exemplar_dist(E, X, R, paths, n_paths, glob_size <= 0 ? 10 : glob_size, res, numtag, shard);
-  if (R.has_extract || R.has_compute)
-    throw PlanError(LK_ERR_UNSUPPORTED, "extract / compute exemplar queries are not on the hot path");
-  const bool logs = R.dataset == "logs";
-  if (!tagnum && !logs && R.dataset != "traces") {
-    // metrics: the projection's second column is "_cardinalhq.name" (BaseExpr.scala:41); getDouble of a metric
-    // name fails the stream, which query-api turns into an empty source (QueryEngineV2.scala:141-145)
-    if (R.dataset == "metrics") throw PlanError(LK_ERR_ARG, "metrics exemplar: getDouble of \"_cardinalhq.name\"");
-    throw PlanError(LK_ERR_ARG, "Invalid dataset: " + R.dataset);
-  }
-  std::string order = R.order;
-  for (auto& c : order) c = char(toupper(static_cast<unsigned char>(c)));
-  if (tagnum) order = "DESC";   // (a tag query has no ORDER BY / LIMIT)
-  if (order != "DESC" && order != "ASC") throw PlanError(LK_ERR_ARG, "ORDER BY direction '" + R.order + "'");
-  if (R.limit < 0 && !tagnum) throw PlanError(LK_ERR_ARG, "negative LIMIT");
-  const bool desc = order == "DESC";
-  const uint64_t limit = tagnum ? 0 : uint64_t(R.limit);
-  const bool per_glob_rows = (flags & LK_PER_GLOB_ROWS) != 0;
-
-  std::vector<const FilterNode*> all_leaves;
-  collect_leaves(R.filter.get(), all_leaves);
-  std::vector<std::string> nums;   // numeric comparison columns (gt/ge/lt/le, BaseExpr.scala:488-498)
-  // numeric tag: its leaves (query-api's `exists` on the tag) are numeric IS NOT NULL leaves; the tag column is a
-  // numeric column of the scan either way
-  auto num_col = [&](const FilterNode* l) { return numeric_op(l->op) || (tagnum && l->k == numtag); };
-  for (auto* l : all_leaves) {
-    if (l->extracted || l->computed) throw PlanError(LK_ERR_UNSUPPORTED, "extracted/computed filter fields");
-    if (tagnum && l->k == numtag && !numeric_op(l->op) && l->op != "exists" && l->op != "has")
-      throw PlanError(LK_ERR_UNSUPPORTED, "string comparison '" + l->op + "' on the numeric tag column " + numtag);
-    if (num_col(l)) {
-      if (std::find(nums.begin(), nums.end(), l->k) == nums.end()) nums.push_back(l->k);
-      continue;
-    }
-    static const char* ok[] = {"eq", "!=", "in", "not_in", "regex", "contains", "has", "exists"};
-    if (std::none_of(std::begin(ok), std::end(ok), [&](const char* o) { return l->op == o; }))
-      throw PlanError(LK_ERR_ARG, "Invalid operator " + l->op);
-  }
-  if (tagnum && std::find(nums.begin(), nums.end(), numtag) == nums.end()) nums.push_back(numtag);
-  res->exemplar = true;
-  res->per_glob = true;
-  if (R.segments.empty()) {   // Commons.scala:393-396: the sentinel DataPoint(-1, -1, {})
-    if (per_glob_rows) {
-      res->alloc_rows(1);
-      res->ts[0] = -1;
-      res->val[0] = -1.0;
-      res->glob[0] = 0;
-      res->gid[0] = 0;
-    }
-    res->stats = "{\"scan_ms\":0,\"total_ms\":0,\"rows_scanned\":0,\"candidates\":0}";
-    return LK_OK;
-  }
-
-  // ---- filter columns (string dictionaries) and the Kleene program ----
-  std::vector<LeafCol> strs;
-  for (auto* l : all_leaves) {
-    if (num_col(l)) continue;
-    auto it = std::find_if(strs.begin(), strs.end(), [&](const LeafCol& s) { return s.name == l->k; });
-    if (it == strs.end()) {
-      strs.push_back(LeafCol{});
-      strs.back().name = l->k;
-      it = strs.end() - 1;
-    }
-    it->leaves.push_back(l);
-  }
-  if (2 + strs.size() + nums.size() > size_t(MAXQCOL))
-    throw PlanError(LK_ERR_UNSUPPORTED, "too many filter columns in one query");
-  for (auto& nm : nums)
-    if (std::find_if(strs.begin(), strs.end(), [&](const LeafCol& sc) { return sc.name == nm; }) != strs.end())
-      throw PlanError(LK_ERR_UNSUPPORTED, "column " + nm + " used both as a string and as a number");
-  if (all_leaves.size() > size_t(MAXLEAF)) throw PlanError(LK_ERR_UNSUPPORTED, "too many filter leaves");
-  // (the numeric tag's `exists` / `has` leaves number as IS NOT NULL leaves: BaseExpr's "<tag>" IS NOT NULL)
-  const LeafNumbering numbered = number_leaves(R.filter.get(), all_leaves, num_col, nums, strs);
-  const std::vector<LeafInfo>& leaves = numbered.leaves;
-  const std::vector<NumLeaf>& nleaves = numbered.nleaves;
-  const std::vector<std::string>& bad_literal = numbered.bad_literal;   // per glob where the field exists
-  const std::vector<uint8_t>& prog = numbered.prog;
-
-  // ---- segments and globs ----
-  // A segment that cannot be read (missing, corrupt, a shape the loader does not take) fails its glob's query only:
-  // that glob is empty, the others stream (Commons.scala:249-253, 338-340).
-  std::vector<std::shared_ptr<Segment>> segs(n_paths);
-  std::vector<uint8_t> seg_bad(n_paths, 0);
-  for (size_t i = 0; i < n_paths; i++) {
-    try {
-      segs[i] = E.get_segment(paths[i], true);
-    } catch (const PlanError& e) {
-      if (e.code != LK_ERR_IO) throw;   // capability gaps / evicted keys fail the call (ADVICE r3)
-      seg_bad[i] = 1;
-    }
-  }
-  if (glob_size <= 0) glob_size = 10;
-  const std::vector<std::string> proj = tagnum ? std::vector<std::string>{kTimestamp, numtag}
-                                       : logs ? std::vector<std::string>{kTimestamp, kValue, kName, kMessage}
-                                              : std::vector<std::string>{kTimestamp, kValue, kSpanName, kSpanKind};
-  const std::set<std::string> fset = field_set(R);
-  std::vector<XGlob> globs;
-  for (size_t i = 0; i < n_paths; i += size_t(glob_size)) {
-    XGlob g;
-    for (size_t j = i; j < std::min(n_paths, i + size_t(glob_size)); j++) g.segs.push_back(int(j));
-    g.win_lo = INT64_MAX;
-    g.win_hi = INT64_MIN;
-    std::vector<std::string> uni;
-    for (int si : g.segs) {
-      g.win_lo = std::min(g.win_lo, R.segments[si].start_ts);
-      g.win_hi = std::max(g.win_hi, R.segments[si].end_ts);
-      if (seg_bad[si]) {
-        g.skip = true;
-        continue;
-      }
-      for (auto& [name, pt] : segs[si]->schema) {
-        if (!g.types.count(name)) uni.push_back(name);
-        // a union this engine does not form (e.g. VARCHAR with a number, which DuckDB unifies to VARCHAR): the call
-        // fails with LK_ERR_UNSUPPORTED so the caller can fall back (ADVICE r3), not an empty glob
-        g.types[name] = union_type(g.types.count(name) ? g.types[name] : -1, pt);
-      }
-    }
-    for (auto& l : leaves)   // nonExistentFields -> literal false (Commons.scala:224, BaseExpr.scala:462-464)
-      if (fset.count(l.node->k) && !g.types.count(l.node->k)) g.leaf_false |= 1u << l.index;
-    for (auto& p : proj)      // Binder Error -> empty glob (Commons.scala:249-253)
-      if (!g.types.count(p)) g.skip = true;
-    for (auto& l : leaves)
-      if (!(g.leaf_false >> l.index & 1u) && !g.types.count(l.node->k)) g.skip = true;
-    for (auto& k : bad_literal)   // normalizedValue failed for a field this glob has
-      if (!(fset.count(k) && !g.types.count(k))) g.skip = true;
-    if (tagnum && g.types.count(numtag) && g.types[numtag] == pq::BYTE_ARRAY)   // VARCHAR in a glob of numbers
-      throw PlanError(LK_ERR_UNSUPPORTED, "tag column " + numtag + " is text in some files and numeric in others");
-    for (auto& nm : nums)   // a VARCHAR compared with a number: Binder Error -> empty glob
-      if (g.types.count(nm) && g.types[nm] == pq::BYTE_ARRAY) g.skip = true;
-    g.cols = proj;
-    for (auto& u : uni)
-      if (std::find(g.cols.begin(), g.cols.end(), u) == g.cols.end()) g.cols.push_back(u);
-    globs.push_back(std::move(g));
-  }
-
-  // ---- per filter column: dictionary value -> leaf bits (cached per (column, leaves) like the aggregate path; a
-  // pattern RE2 rejects throws out of the call) ----
-  std::vector<std::vector<uint32_t>> tabs(strs.size());
-  for (size_t s = 0; s < strs.size(); s++) {
-    GlobalDict& gd = E.dict(strs[s].name);
-    std::lock_guard<std::mutex> dg(gd.mu);
-    const uint32_t dict_n = uint32_t(gd.size());
-    const LockedLeafBits cached = extend_leaf_bits(E, strs[s], gd, dict_n);
-    tabs[s].resize(std::max<uint32_t>(dict_n, 1));
-    for (uint32_t gid = 0; gid < dict_n; gid++) tabs[s][gid] = uint32_t(cached.lb->hit[gid]) << 24;
-  }
-
-  // ---- per-segment descriptors ----
-  std::vector<QSeg> qsegs;
-  std::vector<const Segment*> qseg_seg;
-  std::vector<uint32_t> qseg_pos, qseg_glob;
-  uint64_t rows_scanned = 0;
-  uint32_t max_tiles = 0;
-  // a referenced column this engine does not decode fails the call (LK_ERR_UNSUPPORTED: the caller falls back), where
-  // a column of a type the query cannot bind is DuckDB's Binder Error (empty glob, below)
-  for (size_t gi = 0; gi < globs.size(); gi++) {
-    if (globs[gi].skip) continue;
-    for (int si : globs[gi].segs) {
-      if (!segs[si] || segs[si]->unloaded.empty()) continue;
-      const Segment& S = *segs[si];
-      auto check = [&](const std::string& c) {
-        auto u = S.unloaded.find(c);
-        if (u != S.unloaded.end()) throw PlanError(LK_ERR_UNSUPPORTED, u->second + " (" + S.key + ")");
-      };
-      check(kTimestamp);
-      for (auto& sc : strs) check(sc.name);
-      for (auto& nm : nums) check(nm);
-      for (auto& c : globs[gi].cols) check(c);
-    }
-  }
-  for (size_t gi = 0; gi < globs.size(); gi++) {
-    XGlob& g = globs[gi];
-    if (g.skip || g.win_lo >= g.win_hi || (limit == 0 && !tagnum)) continue;
-    // the glob's descriptors go in together: a column its query cannot bind empties the glob (Binder Error,
-    // Commons.scala:249-253), the other globs are unaffected
-    const size_t mark = qsegs.size();
-    const uint64_t rows_mark = rows_scanned;
-    const uint32_t tiles_mark = max_tiles;
-    try {
-    for (size_t p = 0; p < g.segs.size(); p++) {
-      const Segment& S = *segs[g.segs[p]];
-      QSeg q{};
-      q.base = S.d_data;
-      q.tiles = S.d_tiles;
-      q.ntiles = uint32_t(S.tiles.size());
-      q.glob_slot = uint32_t(gi);
-      q.leaf_false = g.leaf_false;
-      q.win_lo = g.win_lo;
-      q.win_hi = g.win_hi;
-      auto bind = [&](int qc, const std::string& name, bool want_string) {
-        const int c = S.col_index(name);
-        if (c < 0) return;
-        const HostCol& hc = S.cols[c];
-        if (want_string != hc.is_string)
-          throw PlanError(LK_ERR_UNSUPPORTED, "column " + name + " has an unexpected type for its role");
-        if (qc == 0 && hc.ptype != pq::INT64 && hc.ptype != pq::INT32)
-          throw PlanError(LK_ERR_UNSUPPORTED, "timestamp column must be INT64 or INT32");
-        const bool is_tag = tagnum && name == numtag;
-        if (qc >= 2 + int(strs.size()) && hc.ptype != pq::INT64 && hc.ptype != pq::DOUBLE && hc.ptype != pq::INT32 &&
-            hc.ptype != pq::FLOAT && !(is_tag && hc.ptype == pq::BOOLEAN))
-          throw PlanError(LK_ERR_UNSUPPORTED, "numeric comparison on column " + name + " of an undecoded type");
-        uint32_t pad = uint32_t(hc.ptype);
-        if (is_tag) pad |= uint32_t(g.types.count(numtag) ? g.types[numtag] : hc.ptype) << 8;   // the glob's union type
-        q.cols[qc] = QCol{hc.d_pages, hc.d_runs, hc.d_tcols, hc.d_remap, 1u, pad};
-      };
-      bind(0, kTimestamp, false);
-      if (!q.cols[0].present) continue;
-      for (size_t s = 0; s < strs.size(); s++) bind(int(2 + s), strs[s].name, true);
-      for (size_t n = 0; n < nums.size(); n++) bind(int(2 + strs.size() + n), nums[n], false);
-      rows_scanned += uint64_t(S.num_rows);
-      max_tiles = std::max(max_tiles, q.ntiles);
-      qsegs.push_back(q);
-      qseg_seg.push_back(&S);
-      qseg_pos.push_back(uint32_t(p));
-      qseg_glob.push_back(uint32_t(gi));
-    }
-    g.open = true;
-    } catch (const PlanError& e) {
-      if (e.code != LK_ERR_UNSUPPORTED) throw;
-      g.skip = true;
-      qsegs.resize(mark);
-      qseg_seg.resize(mark);
-      qseg_pos.resize(mark);
-      qseg_glob.resize(mark);
-      rows_scanned = rows_mark;
-      max_tiles = tiles_mark;
-    }
-  }
-  if (qsegs.size() > 65535) throw PlanError(LK_ERR_UNSUPPORTED, "more than 65535 segments in one evaluation");
-
-  // ---- device staging ----
-  HIP_TRY(hipSetDevice(E.device));
-  hipStream_t st = X.stream;
-  std::vector<uint32_t> truth;
-  if (leaves.size() <= size_t(TT_MAX_LEAVES)) truth = truth_table(prog, uint32_t(leaves.size()));
-  std::vector<StrParam> strp(strs.size());
-  const size_t ng = globs.size();
-  size_t off = 0;
-  auto reserve = [&](size_t n) { size_t o = (off + 255) / 256 * 256; off = o + n; return o; };
-  const size_t o_segs = reserve(qsegs.size() * sizeof(QSeg));
-  const size_t o_truth = reserve(truth.size() * 4);
-  std::vector<size_t> o_tab(strs.size());
-  for (size_t s = 0; s < strs.size(); s++) o_tab[s] = reserve(tabs[s].size() * 4);
-  const size_t o_strp = reserve(strp.size() * sizeof(StrParam));
-  const size_t o_rng = reserve(ng * 8 * 4);          // rlo, rhi, hbase, hwidth
-  const size_t o_n = reserve(8);
-  const size_t stage_bytes = off;
-  const size_t o_hist = reserve(ng * XBINS * 4);   // host side only: the histogram read back each pass
-  uint8_t* hbuf = static_cast<uint8_t*>(X.pinned_buf(off));
-  uint8_t* dbuf = static_cast<uint8_t*>(X.workspace("xquery", stage_bytes));
-  uint32_t* d_hist = static_cast<uint32_t*>(X.workspace("xhist", std::max<size_t>(ng * XBINS * 4, 4)));
-  memcpy(hbuf + o_segs, qsegs.data(), qsegs.size() * sizeof(QSeg));
-  if (!truth.empty()) memcpy(hbuf + o_truth, truth.data(), truth.size() * 4);
-  for (size_t s = 0; s < strs.size(); s++) {
-    memcpy(hbuf + o_tab[s], tabs[s].data(), tabs[s].size() * 4);
-    strp[s].strtab = reinterpret_cast<const uint32_t*>(dbuf + o_tab[s]);
-    strp[s].lbase = strs[s].lbase;
-    strp[s].lmask = strs[s].lmask;
-    strp[s].hmask = strs[s].hmask;
-  }
-  memcpy(hbuf + o_strp, strp.data(), strp.size() * sizeof(StrParam));
-  int64_t* hr = reinterpret_cast<int64_t*>(hbuf + o_rng);
-  XParams P{};
-  P.segs = reinterpret_cast<const QSeg*>(dbuf + o_segs);
-  P.nsegs = uint32_t(qsegs.size());
-  P.max_tiles = max_tiles;
-  P.strp = reinterpret_cast<const StrParam*>(dbuf + o_strp);
-  P.nstr = uint32_t(strs.size());
-  P.nleaves = uint32_t(leaves.size());
-  P.nprog = uint32_t(prog.size());
-  memcpy(P.prog, prog.data(), prog.size());
-  P.truth = truth.empty() ? nullptr : reinterpret_cast<const uint32_t*>(dbuf + o_truth);
-  P.nnum = uint32_t(nums.size());
-  P.nnl = uint32_t(nleaves.size());
-  for (size_t i = 0; i < nleaves.size(); i++) P.nl[i] = nleaves[i];
-  int64_t* d_rng = reinterpret_cast<int64_t*>(dbuf + o_rng);
-  P.rlo = d_rng;
-  P.rhi = d_rng + ng;
-  P.hbase = d_rng + 2 * ng;
-  P.hwidth = d_rng + 3 * ng;
-  P.out_n = reinterpret_cast<uint32_t*>(dbuf + o_n);
-  P.tag_qc = ~0u;
-
-  if (tagnum) {
-    // ---- tag query over a numeric tag: SELECT "<tag>", COUNT(*) ... GROUP BY "<tag>" per glob (BaseExpr.scala:
-    // 127-138): one TAGNUM pass counts passing rows per (glob, canonical tag value); the host prints each value as JDBC
-    // getString does for the glob's union_by_name type (Long / Integer / Double / Float / Boolean .toString) ----
-    const uint32_t tagk = uint32_t(std::find(nums.begin(), nums.end(), numtag) - nums.begin());
-    P.tag_qc = uint32_t(2 + strs.size() + tagk);
-    uint64_t max_rows = 1;
-    for (size_t gi = 0; gi < ng; gi++) {
-      const XGlob& g = globs[gi];
-      const bool live = !g.skip && g.win_lo < g.win_hi;
-      hr[gi] = live ? g.win_lo : 0;
-      hr[ng + gi] = live ? g.win_hi : 0;
-    }
-    {
-      std::vector<uint64_t> grow(ng, 0);
-      for (size_t q = 0; q < qsegs.size(); q++) grow[qseg_glob[q]] += uint64_t(qseg_seg[q]->num_rows);
-      for (uint64_t r : grow) max_rows = std::max(max_rows, r);
-    }
-    auto pow2 = [](uint64_t x) {
-      uint64_t p = 1;
-      while (p < x) p <<= 1;
-      return p;
-    };
-    const uint64_t cap_max = std::max<uint64_t>(1 << 12, pow2(2 * max_rows));
-    uint64_t tcap = std::min<uint64_t>(cap_max, uint64_t(1) << 12);
-    if (const char* e = getenv("LK_TAGNUM_INIT_SLOTS")) tcap = std::min<uint64_t>(cap_max, pow2(std::max<uint64_t>(64, strtoull(e, nullptr, 10))));
-    HIP_TRY(hipMemcpyAsync(dbuf, hbuf, stage_bytes, hipMemcpyHostToDevice, st));
-    P.mode = XMODE_TAGNUM;
-    float scan_ms = 0.f;
-    int attempts = 0;
-    uint8_t* tb = nullptr;
-    for (;;) {
-      attempts++;
-      const size_t tbytes = ng * tcap * 16 + ng * 16 + 64;
-      tb = static_cast<uint8_t*>(X.workspace("tagnum", tbytes));
-      P.tkeys = reinterpret_cast<unsigned long long*>(tb);
-      P.tcnt = reinterpret_cast<unsigned long long*>(tb + ng * tcap * 8);
-      P.tspec = reinterpret_cast<unsigned long long*>(tb + ng * tcap * 16);
-      P.tflags = reinterpret_cast<uint32_t*>(tb + ng * tcap * 16 + ng * 16);
-      P.tcap = tcap;
-      HIP_TRY(hipMemsetAsync(tb, 0xff, ng * tcap * 8, st));
-      HIP_TRY(hipMemsetAsync(tb + ng * tcap * 8, 0, ng * tcap * 8 + ng * 16 + 64, st));
-      HIP_TRY(hipEventRecord(X.ev_scan0, st));
-      HIP_TRY(launch_ex_scan(P, st));
-      HIP_TRY(hipEventRecord(X.ev_scan1, st));
-      uint32_t fl = 0;
-      HIP_TRY(hipMemcpyAsync(&fl, P.tflags, 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, X.ev_scan0, X.ev_scan1));
-      scan_ms += ms;
-      if (!(fl & FLAG_HASH_FULL)) break;
-      if (tcap >= cap_max) throw PlanError(LK_ERR_MEMORY, "tag value table full at its bound");
-      tcap = std::min(cap_max, tcap * 8);
-    }
-    // occupied slots -> (key, count, glob) records; per-glob NULL / all-ones counts
-    auto* recs = static_cast<unsigned long long*>(X.workspace("tagrecs", ng * tcap * 24 + 64));
-    uint32_t* d_n = reinterpret_cast<uint32_t*>(recs);
-    HIP_TRY(hipMemsetAsync(d_n, 0, 4, st));
-    HIP_TRY(launch_tag_compact(P.tkeys, P.tcnt, tcap, uint32_t(ng), recs + 1, d_n, st));
-    uint32_t nrec = 0;
-    std::vector<unsigned long long> spec(ng * 2);
-    HIP_TRY(hipMemcpyAsync(&nrec, d_n, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(spec.data(), P.tspec, ng * 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<unsigned long long> hrec(size_t(nrec) * 3);
-    if (nrec) {
-      HIP_TRY(hipMemcpyAsync(hrec.data(), recs + 1, size_t(nrec) * 24, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-    }
-    // per glob: (key, count) in the union type's value order, NULL last
-    struct TRow {
-      uint32_t glob;
-      bool null;
-      unsigned long long key;
-      uint64_t count;
-      std::string text;
-    };
-    std::vector<TRow> rows;
-    auto union_of = [&](uint32_t gi) {
-      auto it = globs[gi].types.find(numtag);
-      return it == globs[gi].types.end() ? int(pq::INT64) : it->second;
-    };
-    for (uint32_t i = 0; i < nrec; i++)
-      rows.push_back(TRow{uint32_t(hrec[3 * i + 2]), false, hrec[3 * i], hrec[3 * i + 1], std::string()});
-    for (uint32_t gi = 0; gi < ng; gi++) {
-      if (spec[2 * gi + 1]) rows.push_back(TRow{gi, false, TAG_EMPTY, spec[2 * gi + 1], std::string()});
-      if (spec[2 * gi]) rows.push_back(TRow{gi, true, 0, spec[2 * gi], std::string()});
-    }
-    auto num_of = [&](const TRow& r) -> double {   // value order within a glob
-      const int ut = union_of(r.glob);
-      if (ut == pq::DOUBLE) {
-        double d;
-        memcpy(&d, &r.key, 8);
-        return d;
-      }
-      if (ut == pq::FLOAT) {
-        float f;
-        const uint32_t u = uint32_t(r.key);
-        memcpy(&f, &u, 4);
-        return double(f);
-      }
-      return double(int64_t(r.key));
-    };
-    for (auto& r : rows)
-      if (!r.null) r.text = value_text(r.key, union_of(r.glob), union_of(r.glob));
-    std::sort(rows.begin(), rows.end(), [&](const TRow& a, const TRow& b) {
-      if (a.glob != b.glob) return a.glob < b.glob;
-      if (a.null != b.null) return b.null;
-      if (a.null) return false;
-      const int ut = union_of(a.glob);
-      if (ut != pq::DOUBLE && ut != pq::FLOAT)   // integers (the all-ones key is -1): exact order, not as doubles
-        return int64_t(a.key) < int64_t(b.key);  // (beyond 2^53 doubles tie and the text order is wrong)
-      const double x = num_of(a), y = num_of(b);
-      if (x != y && x == x && y == y) return x < y;
-      return a.text < b.text;
-    });
-    if (!per_glob_rows) {   // merged: counts summed per tag text (NULL apart), in first-seen order
-      std::vector<TRow> m;
-      std::map<std::pair<bool, std::string>, size_t> at;
-      for (auto& r : rows) {
-        auto k = std::make_pair(r.null, r.text);
-        auto it = at.find(k);
-        if (it == at.end()) {
-          at.emplace(k, m.size());
-          m.push_back(r);
-          m.back().glob = 0;
-        } else {
-          m[it->second].count += r.count;
-        }
-      }
-      rows.swap(m);
-    }
-    // rows: Commons.toDataPoint's tag branch (Commons.scala:406-423): the tag (dropped when NULL / "" / "null" or a
-    // noisy name, NoisyTagsDropper) and "count"; value = the count, timestamp = now (as the string tag path)
-    const int64_t now_ms = std::chrono::duration_cast<std::chrono::milliseconds>(
-                               std::chrono::system_clock::now().time_since_epoch()).count();
-    const bool hide = noisy_tag(numtag);
-    res->per_glob = per_glob_rows;
-    res->alloc_rows(rows.size());
-    res->tag_names = {numtag, "count"};
-    res->ex_tags.assign(rows.size() * 2, nullptr);
-    for (size_t i = 0; i < rows.size(); i++) {
-      res->ts[i] = now_ms;
-      res->val[i] = double(rows[i].count);
-      res->glob[i] = rows[i].glob;
-      res->gid[i] = uint32_t(i);
-      if (!rows[i].null && !hide && !null_like(rows[i].text)) {
-        res->owned.push_back(rows[i].text);
-        res->ex_tags[2 * i] = res->owned.back().c_str();
-      }
-      res->owned.push_back(std::to_string((unsigned long long)rows[i].count));
-      res->ex_tags[2 * i + 1] = res->owned.back().c_str();
-    }
-    char buf[320];
-    snprintf(buf, sizeof buf,
-             "{\"scan_ms\":%.4f,\"total_ms\":%.4f,\"rows_scanned\":%llu,\"tag_values\":%u,\"attempts\":%d,"
-             "\"slots\":%llu,\"table\":\"tagnum\",\"failed_globs\":%zu}",
-             double(scan_ms), ms_since(t_start), (unsigned long long)rows_scanned, nrec, attempts,
-             (unsigned long long)tcap, size_t(std::count_if(globs.begin(), globs.end(), [](const XGlob& g) { return g.skip; })));
-    res->stats = buf;
-    return LK_OK;
-  }
-
-  // ---- HIST passes: narrow every glob to the rows that can make its top `limit` ----
-  // rows listed beyond each glob's `limit` at most, unless tied on one millisecond (tests shrink it with
-  // LK_EX_CAND_CAP to exercise the refinement)
-  const uint64_t kCandCap = getenv("LK_EX_CAND_CAP") ? std::max<uint64_t>(1, strtoull(getenv("LK_EX_CAND_CAP"), nullptr, 10))
-                                                     : (uint64_t(1) << 24);
-  hipEvent_t e0 = X.ev_scan0, e1 = X.ev_scan1;
-  float scan_ms = 0.f;
-  int passes = 0;
-  for (auto& g : globs) {
-    g.hlo = g.win_lo;
-    g.hhi = g.win_hi;
-    g.need = limit;
-    g.elo = g.win_lo;
-    g.ehi = g.win_hi;
-  }
-  // Ordered end first: segments are written in time order, so the newest (DESC) rows sit in a few tiles.  From the
-  // zone maps, candidate boundaries covering the last 2^20, 2^23, ... rows of the glob; a HIST pass over
-  // [boundary, window end) that already counts `limit` passing rows holds the whole top `limit` (every row before
-  // the boundary is older than all of them); otherwise the next, wider boundary is tried.
-  {
-    std::vector<std::vector<std::pair<int64_t, int64_t>>> tl(ng);   // (ordered key, other end)
-    std::vector<std::vector<uint32_t>> tr(ng);
-    for (size_t q = 0; q < qsegs.size(); q++) {
-      const XGlob& g = globs[qseg_glob[q]];
-      for (const TileDesc& td : qseg_seg[q]->tiles) {
-        if (td.ts_max < g.win_lo || td.ts_min >= g.win_hi) continue;
-        tl[qseg_glob[q]].emplace_back(desc ? -td.ts_max : td.ts_min, desc ? td.ts_min : td.ts_max);
-        tr[qseg_glob[q]].push_back(td.nrows);
-      }
-    }
-    for (size_t gi = 0; gi < ng; gi++) {
-      XGlob& g = globs[gi];
-      if (!g.open) continue;
-      std::vector<size_t> ord(tl[gi].size());
-      for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
-      std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return tl[gi][a].first < tl[gi][b].first; });
-      uint64_t rows = 0, goal = getenv("LK_EX_PROBE_ROWS") ? std::max<uint64_t>(1, strtoull(getenv("LK_EX_PROBE_ROWS"), nullptr, 10))
-                                                         : (uint64_t(1) << 20);   // env: tests only
-      int64_t edge = desc ? INT64_MAX : INT64_MIN;
-      for (size_t i : ord) {
-        rows += tr[gi][i];
-        edge = desc ? std::min(edge, tl[gi][i].second) : std::max(edge, tl[gi][i].second + 1);
-        if (rows >= goal) {
-          const int64_t b = desc ? std::max(edge, g.win_lo) : std::min(edge, g.win_hi);
-          if ((desc && b > g.win_lo) || (!desc && b < g.win_hi)) g.probes.push_back(b);
-          goal *= 8;
-        }
-      }
-    }
-  }
-  bool first_upload = true;
-  while (std::any_of(globs.begin(), globs.end(), [](const XGlob& g) { return g.open; })) {
-    std::vector<uint32_t> nb(ng, 0);
-    for (size_t gi = 0; gi < ng; gi++) {
-      XGlob& g = globs[gi];
-      if (g.open && g.probe < g.probes.size()) {   // probing: [boundary, end) (DESC) / [start, boundary) (ASC)
-        g.hlo = desc ? g.probes[g.probe] : g.win_lo;
-        g.hhi = desc ? g.win_hi : g.probes[g.probe];
-      }
-      const int64_t span = g.open ? g.hhi - g.hlo : 0;
-      const int64_t w = span > 0 ? (span + XBINS - 1) / XBINS : 1;
-      hr[gi] = g.open ? g.hlo : 0;
-      hr[ng + gi] = g.open ? g.hhi : 0;
-      hr[2 * ng + gi] = g.hlo;
-      hr[3 * ng + gi] = w;
-      nb[gi] = span > 0 ? uint32_t((span + w - 1) / w) : 0u;
-    }
-    HIP_TRY(hipMemcpyAsync(first_upload ? dbuf : dbuf + o_rng, first_upload ? hbuf : hbuf + o_rng,
-                            first_upload ? stage_bytes : ng * 32, hipMemcpyHostToDevice, st));
-    first_upload = false;
-    HIP_TRY(hipMemsetAsync(d_hist, 0, ng * XBINS * 4, st));
-    P.mode = XMODE_HIST;
-    P.nbins = XBINS;
-    P.hist = d_hist;
-    HIP_TRY(hipEventRecord(e0, st));
-    HIP_TRY(launch_ex_scan(P, st));
-    HIP_TRY(hipEventRecord(e1, st));
-    uint32_t* hh = reinterpret_cast<uint32_t*>(hbuf + o_hist);
-    HIP_TRY(hipMemcpyAsync(hh, d_hist, ng * XBINS * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    scan_ms += ms;
-    passes++;
-    for (size_t gi = 0; gi < ng; gi++) {
-      XGlob& g = globs[gi];
-      if (!g.open) continue;
-      const uint32_t* h = hh + gi * XBINS;
-      const int64_t w = hr[3 * ng + gi];
-      if (g.probe < g.probes.size()) {
-        uint64_t tot = 0;
-        for (uint32_t k = 0; k < nb[gi]; k++) tot += h[k];
-        if (tot < g.need) {   // not enough rows past this boundary: a wider one, or the whole window
-          if (++g.probe >= g.probes.size()) {
-            g.hlo = g.win_lo;
-            g.hhi = g.win_hi;
-          }
-          continue;
-        }
-        g.probe = g.probes.size();   // the top `limit` lies in the probed range: narrow it as usual
-      }
-      uint64_t cum = 0;
-      int64_t split = -1;
-      for (uint32_t k = 0; k < nb[gi]; k++) {
-        const uint32_t b = desc ? nb[gi] - 1 - k : k;
-        if (cum + h[b] >= g.need) {
-          split = int64_t(b);
-          break;
-        }
-        cum += h[b];
-      }
-      if (split < 0) {   // fewer rows than wanted: every row of the range
-        g.count = g.above + cum;
-        if (desc) g.elo = g.hlo;
-        else g.ehi = g.hhi;
-        g.open = false;
-        continue;
-      }
-      const int64_t blo = g.hlo + split * w, bhi = std::min(g.hhi, blo + w);
-      // the split bin is taken whole when the rows it adds beyond the `need` still wanted stay under the cap (or it
-      // is one millisecond wide: those rows are tied and all listed)
-      const uint64_t with_bin = g.above + cum + h[split];
-      if (cum + h[split] - g.need <= kCandCap || w == 1) {
-        g.count = with_bin;
-        if (desc) g.elo = blo;
-        else g.ehi = bhi;
-        g.open = false;
-      } else {
-        g.above += cum;
-        g.need -= cum;
-        g.hlo = blo;
-        g.hhi = bhi;
-      }
-    }
-  }
-
-  // ---- EMIT: the candidates of every glob's final range ----
-  uint64_t total = 0;
-  for (auto& g : globs) total += g.count;
-  if (total > (uint64_t(1) << 28)) throw PlanError(LK_ERR_UNSUPPORTED, "too many exemplar candidates");
-  std::vector<Cand> cands;
-  if (total) {
-    for (size_t gi = 0; gi < ng; gi++) {
-      const XGlob& g = globs[gi];
-      const bool live = g.count > 0;
-      hr[gi] = live ? g.elo : 0;
-      hr[ng + gi] = live ? g.ehi : 0;
-    }
-    unsigned long long* d_out = static_cast<unsigned long long*>(X.workspace("xcand", total * 16));
-    HIP_TRY(hipMemcpyAsync(dbuf + o_rng, hbuf + o_rng, ng * 16, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(dbuf + o_n, 0, 8, st));
-    P.mode = XMODE_EMIT;
-    P.out = d_out;
-    P.cap = uint32_t(total);
-    HIP_TRY(hipEventRecord(e0, st));
-    HIP_TRY(launch_ex_scan(P, st));
-    HIP_TRY(hipEventRecord(e1, st));
-    // pinned destinations: a device-to-host copy into pageable memory goes through the runtime's staging buffers
-    PinnedTmp eo(total * 16 + 64);
-    const unsigned long long* h_out = static_cast<const unsigned long long*>(eo.p());
-    HIP_TRY(hipMemcpyAsync(eo.p(), d_out, total * 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(eo.p()) + total * 16, dbuf + o_n, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    uint32_t got = 0;
-    memcpy(&got, static_cast<const uint8_t*>(eo.p()) + total * 16, 4);
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    scan_ms += ms;
-    if (got != total) throw PlanError(LK_ERR_DEVICE, "internal: exemplar candidate count disagrees with the histogram");
-    cands.resize(total);
-    for (uint64_t i = 0; i < total; i++) {
-      const unsigned long long ref = h_out[2 * i + 1];
-      const uint32_t qs = uint32_t(ref >> 48), tile = uint32_t((ref >> 16) & 0xffffffffu), r = uint32_t(ref & 0xffffu);
-      const Segment& S = *qseg_seg[qs];
-      const TileDesc& td = S.tiles[tile];
-      uint64_t row = uint64_t(td.row0) + r;
-      for (uint32_t k = 0; k < td.rg; k++) row += uint64_t(S.rg_rows[k]);
-      cands[i] = Cand{int64_t(h_out[2 * i]), qs, qseg_pos[qs], row, ref};
-    }
-  }
-
-  // ---- per glob: the top `limit` in ORDER BY order (ties: file order) ----
-  std::vector<std::vector<const Cand*>> per(ng);
-  for (auto& c : cands) per[qseg_glob[c.qseg]].push_back(&c);
-  for (auto& v : per) {
-    std::sort(v.begin(), v.end(), [&](const Cand* a, const Cand* b) {
-      if (a->ts != b->ts) return desc ? a->ts > b->ts : a->ts < b->ts;
-      if (a->pos != b->pos) return a->pos < b->pos;
-      return a->row < b->row;
-    });
-    if (v.size() > limit) v.resize(size_t(limit));
-  }
-  // Akka mergeSorted fold over the globs' streams (Commons.scala:391-392): merge(merge(merge([], g0), g1), g2)...,
-  // each merge emitting the left head when it is strictly less under the ordering, the right head otherwise.
-  const bool rev = R.reverse_sort;   // rollupAgg is empty for exemplars (Commons.scala:125-129)
-  auto less = [&](const Cand* a, const Cand* b) { return rev ? a->ts > b->ts : a->ts < b->ts; };
-  std::vector<const Cand*> stream;
-  for (auto& v : per) {
-    std::vector<const Cand*> m;
-    m.reserve(stream.size() + v.size());
-    size_t i = 0, j = 0;
-    while (i < stream.size() && j < v.size()) {
-      if (less(stream[i], v[j])) m.push_back(stream[i++]);
-      else m.push_back(v[j++]);
-    }
-    while (i < stream.size()) m.push_back(stream[i++]);
-    while (j < v.size()) m.push_back(v[j++]);
-    stream.swap(m);
-  }
-
-  // ---- gather every output column of the selected rows ----
-  std::vector<std::string> out_cols;
-  for (auto& g : globs) {
-    if (g.skip) continue;
-    for (auto& c : g.cols)
-      if (std::find(out_cols.begin(), out_cols.end(), c) == out_cols.end()) out_cols.push_back(c);
-  }
-  const size_t nsel = stream.size(), ncols = out_cols.size();
-  std::vector<unsigned long long> gval(nsel * ncols);
-  std::vector<uint8_t> gok(nsel * ncols);
-  if (nsel && ncols) {
-    std::vector<GCol> gcols(qsegs.size() * ncols);
-    for (size_t q = 0; q < qsegs.size(); q++) {
-      const Segment& S = *qseg_seg[q];
-      for (size_t k = 0; k < ncols; k++) {
-        GCol& gc = gcols[q * ncols + k];
-        const int c = S.col_index(out_cols[k]);
-        if (c < 0) {
-          if (S.all_columns.count(out_cols[k]))
-            throw PlanError(LK_ERR_UNSUPPORTED, "column " + out_cols[k] + " has a physical type the engine does not load");
-          continue;
-        }
-        const HostCol& hc = S.cols[c];
-        gc = GCol{S.d_data, hc.d_runs, hc.d_tcols, hc.d_remap, 1u, 0u};
-      }
-    }
-    const size_t gb = gcols.size() * sizeof(GCol), sb = nsel * 8, vb = nsel * ncols * 8, ob = nsel * ncols;
-    PinnedTmp gio(gb + sb + vb + ob + 64);   // pinned staging both ways: [columns | selected refs | values | ok]
-    uint8_t* hg = static_cast<uint8_t*>(gio.p());
-    memcpy(hg, gcols.data(), gb);
-    for (size_t i = 0; i < nsel; i++) reinterpret_cast<unsigned long long*>(hg + gb)[i] = stream[i]->ref;
-    uint8_t* dg = static_cast<uint8_t*>(X.workspace("xgather", gb + sb + vb + ob + 1024));
-    HIP_TRY(hipMemcpyAsync(dg, hg, gb + sb, hipMemcpyHostToDevice, st));
-    GParams G{};
-    G.cols = reinterpret_cast<const GCol*>(dg);
-    G.sel = reinterpret_cast<const unsigned long long*>(dg + gb);
-    G.nsel = uint32_t(nsel);
-    G.ncols = uint32_t(ncols);
-    G.val = reinterpret_cast<unsigned long long*>(dg + gb + sb);
-    G.ok = dg + gb + sb + vb;
-    HIP_TRY(launch_ex_gather(G, st));
-    HIP_TRY(hipMemcpyAsync(hg + gb + sb, G.val, vb + ob, hipMemcpyDeviceToHost, st));   // values and ok flags
-    HIP_TRY(hipStreamSynchronize(st));
-    memcpy(gval.data(), hg + gb + sb, vb);
-    memcpy(gok.data(), hg + gb + sb + vb, ob);
-  }
-
-  // ---- rows: timestamp, getDouble(value) (SQL NULL -> 0.0), tags as JDBC getString text ----
-  res->alloc_rows(nsel);
-  res->tag_names = out_cols;
-  res->ex_tags.assign(nsel * ncols, nullptr);
-  const size_t vcol = size_t(std::find(out_cols.begin(), out_cols.end(), std::string(kValue)) - out_cols.begin());
-  for (size_t i = 0; i < nsel; i++) {
-    const Cand& c = *stream[i];
-    res->ts[i] = c.ts;
-    res->glob[i] = qseg_glob[c.qseg];
-    res->gid[i] = uint32_t(i);
-    res->val[i] = 0.0;
-  }
-  // column by column: each (segment, column)'s physical / union type looked up once, each dictionary locked once
-  std::vector<const HostCol*> qcol(qsegs.size());
-  std::vector<int> qut(qsegs.size());
-  for (size_t k = 0; k < ncols; k++) {
-    const std::string& name = out_cols[k];
-    bool any_string = false;
-    for (size_t q = 0; q < qsegs.size(); q++) {
-      const Segment& S = *qseg_seg[q];
-      const int ci = S.col_index(name);
-      qcol[q] = ci < 0 ? nullptr : &S.cols[size_t(ci)];
-      if (!qcol[q]) continue;
-      const XGlob& g = globs[qseg_glob[q]];
-      const auto ut = g.types.find(name);
-      qut[q] = ut == g.types.end() ? qcol[q]->ptype : ut->second;
-      any_string = any_string || qcol[q]->is_string;
-    }
-    GlobalDict* gd = any_string ? &E.dict(name) : nullptr;
-    std::unique_lock<std::mutex> dl;
-    if (gd) {
-      dl = std::unique_lock<std::mutex>(gd->mu);
-      res->keep.push_back(gd->vals);   // tag text outlives a compaction
-    }
-    for (size_t i = 0; i < nsel; i++) {
-      if (!gok[i * ncols + k]) continue;
-      const uint32_t q = stream[i]->qseg;
-      const HostCol& hc = *qcol[q];
-      const unsigned long long raw = gval[i * ncols + k];
-      if (k == vcol) res->val[i] = value_double(raw, hc.ptype);
-      if (hc.is_string) {
-        if (qut[q] != pq::BYTE_ARRAY) throw PlanError(LK_ERR_UNSUPPORTED, "union_by_name over string and numeric " + name);
-        const std::string& s = (*gd)[size_t(raw)];
-        if (!null_like(s)) res->ex_tags[i * ncols + k] = s.c_str();   // Commons.scala:433
-      } else {
-        res->owned.push_back(value_text(raw, hc.ptype, qut[q]));
-        res->ex_tags[i * ncols + k] = res->owned.back().c_str();
-      }
-    }
-  }
-  char buf[256];
-  snprintf(buf, sizeof buf,
-           "{\"scan_ms\":%.4f,\"total_ms\":%.4f,\"rows_scanned\":%llu,\"candidates\":%llu,\"hist_passes\":%d}",
-           double(scan_ms), ms_since(t_start), (unsigned long long)rows_scanned, (unsigned long long)total, passes);
-  res->stats = buf;
+  const EvalCall C{E, X, R, paths, n_paths, glob_size <= 0 ? 10 : glob_size, flags, shard, dist, 0, res,
+                   std::chrono::steady_clock::now()};
+  double scan_ms = 0;
+  if (dist) exemplar_dist(C, numtag);
+  else exemplar_local(C, numtag, &scan_ms);
   return LK_OK;
 }
 
