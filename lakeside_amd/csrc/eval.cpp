@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <set>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -215,9 +216,9 @@ void stage_upload(const EvalCall& C, const Plan& pl, DevState& dv) {
   dv.o_rank = reserve(pl.dp.name_rank.size() * 4);
   // null-like group values folded after per-glob aggregation (merged min/max over NULL-able values)
   std::vector<uint32_t> flat;
-  dv.map_off.assign(pl.fp.cols.size(), SIZE_MAX);
+  dv.map_off.assign(pl.dp.dims.size(), SIZE_MAX);
   if (pl.cs.rekey)
-    for (size_t s = 0; s < pl.fp.cols.size(); s++)
+    for (size_t s = 0; s < pl.dp.dims.size(); s++)
       if (!pl.cs.fold_maps[s].empty()) {
         dv.map_off[s] = flat.size();
         flat.insert(flat.end(), pl.cs.fold_maps[s].begin(), pl.cs.fold_maps[s].end());
@@ -464,6 +465,133 @@ void zero_table(const EvalCall& C, DevState& dv, size_t ncl, bool hashed) {
   HIP_TRY(launch_fill_many(F, dv.st));
 }
 
+// The general row scan's parameters over the staged query (gsegs): XMODE_AGG into dv.P's table, or the numeric group
+// dimensions' discovery (XMODE_NUMDIM), which reads the same rows.
+XParams general_scan_params(const Plan& pl, const DevState& dv, uint32_t mode) {
+  XParams XG{};
+  XG.segs = reinterpret_cast<const QSeg*>(dv.dbuf + dv.o_gsegs);
+  XG.nsegs = uint32_t(pl.sg.gsegs.size());
+  XG.max_tiles = pl.sg.gmax_tiles;
+  XG.strp = dv.P.strp;
+  XG.nstr = dv.P.nstr;
+  XG.nleaves = dv.P.nleaves;
+  XG.nprog = dv.P.nprog;
+  memcpy(XG.prog, dv.P.prog, sizeof(XG.prog));
+  XG.truth = pl.fp.truth_x.empty() ? dv.P.truth : reinterpret_cast<const uint32_t*>(dv.dbuf + dv.o_truth_x);
+  XG.mode = mode;
+  XG.nnum = uint32_t(pl.qs.nums.size());
+  XG.nnl = uint32_t(pl.fp.nleaves.size());
+  for (size_t i = 0; i < pl.fp.nleaves.size(); i++) XG.nl[i] = pl.fp.nleaves[i];
+  XG.agg = dv.kagg;
+  XG.hash = pl.cs.hash_mode ? 1 : 0;
+  XG.q = dv.P;
+  if (pl.qs.fchart) {   // `<field> IS NOT NULL` as a conjunct; a VARCHAR field's values from the staged table
+    XG.field = 1;
+    XG.ftab = dv.ftext_tab ? reinterpret_cast<const double*>(dv.dbuf + dv.o_fval) : nullptr;
+    XG.fok = dv.ftext_tab ? reinterpret_cast<const uint32_t*>(dv.dbuf + dv.o_fok) : nullptr;
+  }
+  // numeric group dimensions: query column, stride and NULL id per dimension; the discovered tables
+  XG.nnd = uint32_t(pl.qs.numgbs.size());
+  for (size_t k = 0; k < pl.qs.numgbs.size(); k++) {
+    const DimCol& dc = pl.dp.dims[pl.fp.cols.size() + k];
+    const size_t n = size_t(std::find(pl.qs.nums.begin(), pl.qs.nums.end(), pl.qs.numgbs[k]) - pl.qs.nums.begin());
+    XG.nd[k] = NumDim{uint32_t(2 + pl.fp.cols.size() + n), uint32_t(dc.stride), dc.dim_null, 0u};
+    XG.ndmask |= 1u << XG.nd[k].qc;
+  }
+  XG.seg_glob = pl.dp.nd.d_seg_glob;
+  XG.ndcap = pl.dp.nd.cap;
+  XG.ndkeys = pl.dp.nd.d_keys;
+  XG.ndids = pl.dp.nd.d_ids;
+  XG.ndones = pl.dp.nd.d_ones;
+  XG.ndflags = pl.dp.nd.d_flags;
+  return XG;
+}
+
+// Numeric group dimensions, the discovery pass: one XMODE_NUMDIM launch over the staged query lists the
+// canonical keys of every numeric group column per glob (tables regrown x8 while one overflows, as TAGNUM's); the host
+// prints each (glob union type, key) as JDBC getString does, orders the distinct texts of all globs -- a dimension's
+// ids depend on the set of texts alone -- and uploads the id of every slot for the aggregate scan's lookup.
+void discover_numdims(const EvalCall& C, Plan& pl, const DevState& dv) {
+  const auto t0 = std::chrono::steady_clock::now();
+  NumDimTables& nd = pl.dp.nd;
+  const size_t nnd = pl.qs.numgbs.size(), ng = pl.gp.globs.size(), nseg = pl.sg.gsegs.size();
+  const size_t first = pl.fp.cols.size();
+  auto pow2 = [](uint64_t x) {
+    uint64_t p = 1;
+    while (p < x) p <<= 1;
+    return p;
+  };
+  std::vector<uint64_t> grows(ng, 0);
+  for (size_t gi = 0; gi < ng; gi++)
+    for (int si : pl.gp.globs[gi].segs)
+      if (pl.gp.segs[si]) grows[gi] += uint64_t(pl.gp.segs[si]->num_rows);
+  const uint64_t cap_max = std::max<uint64_t>(1 << 12, pow2(2 * *std::max_element(grows.begin(), grows.end())));
+  uint64_t cap = std::min<uint64_t>(cap_max, pow2(env_u64("LK_NUMDIM_INIT_SLOTS", uint64_t(1) << 12, 64)));
+  std::vector<unsigned long long> keys;
+  std::vector<uint32_t> ones(ng * nnd, 0);
+  hipStream_t st = dv.st;
+  if (nseg && pl.cs.ncells && (!dv.hbuf || !dv.dbuf)) throw PlanError(LK_ERR_DEVICE, "internal: numeric groupBy without a staged query");
+  for (;;) {
+    nd.attempts++;
+    const size_t nslots = ng * nnd * size_t(cap);
+    // [keys | ids | all-ones words | flags | segment -> glob]
+    const size_t o_ids = nslots * 8, o_ones = o_ids + nslots * 4, o_flags = o_ones + ng * nnd * 4, o_sg = o_flags + 16;
+    uint8_t* tb = static_cast<uint8_t*>(C.X.workspace("numdim", o_sg + nseg * 4 + 64));
+    nd.cap = cap;
+    nd.d_keys = reinterpret_cast<unsigned long long*>(tb);
+    nd.d_ids = reinterpret_cast<uint32_t*>(tb + o_ids);
+    nd.d_ones = reinterpret_cast<uint32_t*>(tb + o_ones);
+    nd.d_flags = reinterpret_cast<uint32_t*>(tb + o_flags);
+    nd.d_seg_glob = reinterpret_cast<const uint32_t*>(tb + o_sg);
+    HIP_TRY(hipMemsetAsync(tb, 0xff, nslots * 8, st));
+    HIP_TRY(hipMemsetAsync(tb + o_ids, 0, o_sg - o_ids, st));
+    if (nseg) HIP_TRY(hipMemcpyAsync(tb + o_sg, pl.sg.gseg_glob.data(), nseg * 4, hipMemcpyHostToDevice, st));
+    if (pl.cs.ncells && nseg) HIP_TRY(launch_ex_scan_numdim(general_scan_params(pl, dv, XMODE_NUMDIM), st));
+    uint32_t fl = 0;
+    HIP_TRY(hipMemcpyAsync(&fl, nd.d_flags, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!(fl & FLAG_HASH_FULL)) break;
+    if (cap >= cap_max) throw PlanError(LK_ERR_MEMORY, "numeric groupBy: value table full at its bound");
+    cap = std::min(cap_max, cap * 8);
+  }
+  const size_t nslots = ng * nnd * size_t(nd.cap);
+  keys.resize(nslots);
+  HIP_TRY(hipMemcpyAsync(keys.data(), nd.d_keys, nslots * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(ones.data(), nd.d_ones, ones.size() * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  std::vector<uint32_t> ids(nslots, 0);
+  for (size_t k = 0; k < nnd; k++) {
+    DimCol& dc = pl.dp.dims[first + k];
+    auto text_of = [&](size_t gi, unsigned long long key) {
+      const int ut = pl.gp.num_ut[k][gi];
+      if (ut < 0) throw PlanError(LK_ERR_DEVICE, "internal: numeric groupBy value in a glob without the column");
+      return value_text(key, ut, ut);
+    };
+    std::set<std::string> texts;
+    for (size_t gi = 0; gi < ng; gi++) {
+      const unsigned long long* tk = keys.data() + (gi * nnd + k) * size_t(nd.cap);
+      for (size_t s2 = 0; s2 < nd.cap; s2++)
+        if (tk[s2] != TAG_EMPTY) texts.insert(text_of(gi, tk[s2]));
+      if (ones[gi * nnd + k]) texts.insert(text_of(gi, TAG_EMPTY));
+    }
+    dc.cand.assign(texts.begin(), texts.end());   // sorted: dim id = position
+    if (dc.cand.size() + 1 > DIM_MASK) throw PlanError(LK_ERR_UNSUPPORTED, "group dimension too large");
+    dc.ndim = uint32_t(dc.cand.size()) + 1;
+    dc.dim_null = uint32_t(dc.cand.size());
+    auto id_of = [&](const std::string& t) { return uint32_t(std::lower_bound(dc.cand.begin(), dc.cand.end(), t) - dc.cand.begin()); };
+    for (size_t gi = 0; gi < ng; gi++) {
+      const size_t base = (gi * nnd + k) * size_t(nd.cap);
+      for (size_t s2 = 0; s2 < nd.cap; s2++)
+        if (keys[base + s2] != TAG_EMPTY) ids[base + s2] = id_of(text_of(gi, keys[base + s2]));
+      ones[gi * nnd + k] = ones[gi * nnd + k] ? id_of(text_of(gi, TAG_EMPTY)) : dc.dim_null;
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(nd.d_ids, ids.data(), nslots * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(nd.d_ones, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  nd.ms = ms_since(t0);
+}
+
 // Zero the table and scan; returns the kernel's flags.
 uint32_t run_scan(const EvalCall& C, const Plan& pl, DevState& dv) {
   dv.nc = pl.cs.hash_mode ? size_t(dv.cap) : size_t(std::max<uint64_t>(pl.cs.ncells, 1));
@@ -487,29 +615,8 @@ uint32_t run_scan(const EvalCall& C, const Plan& pl, DevState& dv) {
   dv.launch_ms = ms_since(C.t_start);   // host staging done, scan enqueued
   if (pl.cs.ncells && !pl.sg.qsegs.empty()) HIP_TRY(launch_scan(dv.P, dv.kagg, dv.st));
   if (pl.cs.ncells && !pl.sg.gsegs.empty()) {   // general row scan (numeric comparison leaves, union_by_name promotion)
-    XParams XG{};
-    XG.segs = reinterpret_cast<const QSeg*>(dv.dbuf + dv.o_gsegs);
-    XG.nsegs = uint32_t(pl.sg.gsegs.size());
-    XG.max_tiles = pl.sg.gmax_tiles;
-    XG.strp = dv.P.strp;
-    XG.nstr = dv.P.nstr;
-    XG.nleaves = dv.P.nleaves;
-    XG.nprog = dv.P.nprog;
-    memcpy(XG.prog, dv.P.prog, sizeof(XG.prog));
-    XG.truth = pl.fp.truth_x.empty() ? dv.P.truth : reinterpret_cast<const uint32_t*>(dv.dbuf + dv.o_truth_x);
-    XG.mode = XMODE_AGG;
-    XG.nnum = uint32_t(pl.qs.nums.size());
-    XG.nnl = uint32_t(pl.fp.nleaves.size());
-    for (size_t i = 0; i < pl.fp.nleaves.size(); i++) XG.nl[i] = pl.fp.nleaves[i];
-    XG.agg = dv.kagg;
-    XG.hash = pl.cs.hash_mode ? 1 : 0;
-    XG.q = dv.P;
-    if (pl.qs.fchart) {   // `<field> IS NOT NULL` as a conjunct; a VARCHAR field's values from the staged table
-      XG.field = 1;
-      XG.ftab = dv.ftext_tab ? reinterpret_cast<const double*>(dv.dbuf + dv.o_fval) : nullptr;
-      XG.fok = dv.ftext_tab ? reinterpret_cast<const uint32_t*>(dv.dbuf + dv.o_fok) : nullptr;
-    }
-    HIP_TRY(launch_ex_scan(XG, dv.st));
+    const XParams XG = general_scan_params(pl, dv, XMODE_AGG);
+    HIP_TRY(XG.nnd ? launch_ex_scan_numdim(XG, dv.st) : launch_ex_scan(XG, dv.st));
   }
   HIP_TRY(hipEventRecord(C.X.ev_scan1, dv.st));
   // small dense single-GPU tables: fixup, rows and flags in one single-workgroup launch (launch_epilogue_small),
@@ -644,6 +751,7 @@ void scan_agreed(const EvalCall& C, const Plan& pl, DevState& dv) {
   }
   if ((dv.hflags & FLAG_MIN_NAN) && pl.qs.agg == AGG_MIN && pl.qs.merged && !pl.cs.min_max_nulls) throw MinNanApart{};
   if (dv.hflags & FLAG_CELL_RANGE) throw PlanError(LK_ERR_DEVICE, "internal: bucket outside the table");
+  if (dv.hflags & FLAG_NUMDIM_MISS) throw PlanError(LK_ERR_DEVICE, "internal: a numeric groupBy value the discovery pass did not list");
   if (dv.hflags & FLAG_HASH_FULL) throw PlanError(LK_ERR_MEMORY, "aggregation hash table full at its bound");
   // DDSketch.accept on NaN / a magnitude beyond the mapping's range throws in the worker's stream stage: the
   // stream fails (Commons.scala:331-335) and query-api sees an empty source
@@ -824,9 +932,9 @@ void ces_rows(const EvalCall& C, const Plan& pl, DevState& dv) {
   // key string of each cell: groupBys.map(g => tags.getOrElse(g, "")).mkString(":") (Aggregator.scala:53-56)
   std::vector<std::string> kstr(dv.nocc);
   for (size_t gi2 = 0; gi2 < C.R.group_bys.size(); gi2++) {
-    const size_t ci = size_t(pl.fp.col_index(C.R.group_bys[gi2]));
+    const size_t ci = size_t(pl.dim_index(C.R.group_bys[gi2]));
     const DimCol& sc = pl.dp.dims[ci];
-    GlobalDict& gd = C.E.dict(pl.fp.cols[ci].name);
+    GlobalDict& gd = C.E.dict(pl.dim_name(ci));
     std::lock_guard<std::mutex> g(gd.mu);
     for (size_t i = 0; i < dv.nocc; i++) {
       const uint32_t d = uint32_t((keys[i] % pl.dp.ngroups) / (sc.stride ? sc.stride : 1) % sc.ndim);
@@ -863,7 +971,7 @@ void sketch_rows(const EvalCall& C, const Plan& pl, DevState& dv) {
   for (size_t i = 0; i < dv.nocc; i++) cellv[i] = keys[i] / DD_NBINS;
   const bool by_name = pl.fp.gbs.empty();
   const bool name_grouped = std::find(pl.fp.gbs.begin(), pl.fp.gbs.end(), std::string(kName)) != pl.fp.gbs.end();
-  for (size_t si = 0; si < pl.fp.cols.size(); si++) {
+  for (size_t si = 0; si < pl.dp.dims.size(); si++) {
     const DimCol& sc = pl.dp.dims[si];
     if (!sc.is_dim || !sc.stride) continue;
     const bool drop = si == 0 && !by_name && !name_grouped;   // name is no key tag when groupBys exist
@@ -875,7 +983,7 @@ void sketch_rows(const EvalCall& C, const Plan& pl, DevState& dv) {
       // step, every name in it: no group term (the tag column reads "" for every row: label_rows' tcols[0]).
       continue;
     }
-    GlobalDict& gd = C.E.dict(pl.fp.cols[si].name);
+    GlobalDict& gd = C.E.dict(pl.dim_name(si));
     std::lock_guard<std::mutex> g(gd.mu);
     std::unordered_map<uint32_t, bool> nl;
     for (size_t i = 0; i < dv.nocc; i++) {
@@ -930,8 +1038,9 @@ void finalize_dense(const EvalCall& C, const Plan& pl, DevState& dv) {
     RP.ngroups = pl.dp.ngroups;
     RP.agg = dv.kagg;
     RP.exist_cnt = dv.fexist;
-    for (size_t s = 0; s < pl.fp.cols.size(); s++) {
+    for (size_t s = 0; s < pl.dp.dims.size(); s++) {
       if (!pl.dp.dims[s].is_dim) continue;
+      if (RP.ndims >= MAXSTR) throw PlanError(LK_ERR_UNSUPPORTED, "too many group dimensions for merged min / max over NULL-able values");
       RP.stride[RP.ndims] = pl.dp.dims[s].stride;
       RP.ndim[RP.ndims] = pl.dp.dims[s].ndim;
       RP.map[RP.ndims] = dv.map_off[s] == SIZE_MAX ? nullptr : dv.d_maps + dv.map_off[s];
@@ -971,8 +1080,9 @@ void finalize_sparse(const EvalCall& C, const Plan& pl, DevState& dv) {
   dv.S.per_glob = pl.qs.per_glob_rows ? 1 : 0;
   dv.S.collapse = pl.cs.collapse ? 1 : 0;
   dv.S.rekey = pl.cs.rekey ? 1 : 0;
-  for (size_t s = 0; s < pl.fp.cols.size() && pl.cs.rekey; s++) {
+  for (size_t s = 0; s < pl.dp.dims.size() && pl.cs.rekey; s++) {
     if (!pl.dp.dims[s].is_dim) continue;
+    if (dv.S.ndims >= MAXSTR) throw PlanError(LK_ERR_UNSUPPORTED, "too many group dimensions for merged min / max over NULL-able values");
     dv.S.stride[dv.S.ndims] = pl.dp.dims[s].stride;
     dv.S.ndim[dv.S.ndims] = pl.dp.dims[s].ndim;
     dv.S.map[dv.S.ndims] = dv.map_off[s] == SIZE_MAX ? nullptr : dv.d_maps + dv.map_off[s];
@@ -1122,6 +1232,15 @@ void write_stats(const EvalCall& C, const Plan& pl, const DevState& dv, const Co
   if (!pl.gp.bad_msg.empty()) C.res->stats += ",\"first_glob_error\":\"" + json_escape(pl.gp.bad_msg) + "\"";
   if (C.redo) C.res->stats += ",\"redo\":" + std::to_string(C.redo);   // 1: metrics at 1 ms, 2: MIN cells kept per glob
   if (dv.dense_shape) C.res->stats += ",\"lean_dense_shape\":1";
+  if (!pl.qs.numgbs.empty()) {
+    std::string nd = ",\"numeric_dims\":[";
+    for (size_t k = 0; k < pl.qs.numgbs.size(); k++)
+      nd += std::string(k ? "," : "") + "{\"column\":\"" + json_escape(pl.qs.numgbs[k]) + "\",\"values\":" +
+            std::to_string(pl.dp.dims[pl.fp.cols.size() + k].cand.size()) + "}";
+    char b3[96];
+    snprintf(b3, sizeof(b3), "],\"numdim_ms\":%.6f,\"numdim_attempts\":%d", pl.dp.nd.ms, pl.dp.nd.attempts);
+    C.res->stats += nd + b3;
+  }
   C.res->stats += "}";
 }
 }  // namespace
@@ -1157,8 +1276,9 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   Plan pl;   // owns the segments and the FieldTab lock until the call returns
   shape_gate(C, pl.qs);
   if (answer_without_segments(C, pl.qs)) return LK_OK;
-  plan_filter(C, pl.qs, pl.fp);
   load_segments(C, pl.qs, pl.gp);
+  plan_numeric_group_bys(C, pl.qs, pl.gp);   // (before the filter's string columns are listed)
+  plan_filter(C, pl.qs, pl.fp);
   if (!pl.gp.tag_numeric || dist) {
     stage("segments");
     plan_globs(C, pl.qs, pl.fp, pl.gp);
@@ -1183,6 +1303,17 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
 
   DevState dv;
   stage_upload(C, pl, dv);
+  if (!pl.qs.numgbs.empty()) {
+    // numeric group dimensions: their values from a discovery pass over the staged query; the group space, cells and
+    // table mode then follow from the dimensions' sizes, and the query is staged again with the final strides
+    discover_numdims(C, pl, dv);
+    plan_strides(pl.dp);
+    plan_cells(C, pl.qs, pl.fp, pl.gp, pl.dp, pl.cs);
+    plan_table_mode(pl.qs, pl.sg, pl.cs);
+    dv = DevState{};
+    stage_upload(C, pl, dv);
+    stage("numdims");
+  }
   if (pl.gp.ftab_guard.owns_lock()) pl.gp.ftab_guard.unlock();   // the table is staged: other calls may extend it
   setup_scan(C, pl, dv);
   scan_agreed(C, pl, dv);   // throws the re-runs (MetricsUnaligned / MinNanApart) before anything is written to *res

@@ -200,7 +200,7 @@ int evaluate_metrics_pct(Engine& E, const std::string& json, const Request& R, c
   auto sub = std::make_shared<Request>(parse_request(json));
   sub->aggregation = "max";
   lk_result r;
-  evaluate_req(E, sub, paths, n_paths, glob_size, LK_PER_GLOB_ROWS | kEvalDistPerGlob, shard, dist, &r);
+  evaluate_req(E, sub, paths, n_paths, glob_size, LK_PER_GLOB_ROWS | kEvalDistPerGlob | kEvalMetricsPct, shard, dist, &r);
   using Tags = std::vector<std::pair<std::string, std::string>>;
   struct Row {
     int64_t ts;

@@ -377,7 +377,8 @@ void plan_filter(const EvalCall& C, const QueryShape& qs, FilterPlan& fp) {
     if (!numeric_op(l->op)) col(l->k).leaves.push_back(l);
   for (auto& g : C.R.group_bys)
     if (std::find(fp.gbs.begin(), fp.gbs.end(), g) == fp.gbs.end()) fp.gbs.push_back(g);
-  for (auto& g : fp.gbs) col(g);
+  for (auto& g : fp.gbs)
+    if (qs.numgb_index(g) < 0) col(g);   // (a numeric group dimension is a numeric query column, no string column)
   if (fp.cols.size() > size_t(MAXSTR)) throw PlanError(LK_ERR_UNSUPPORTED, "too many string columns in one query");
   for (auto& nm : qs.nums)   // a column compared both as a string and as a number fails the glob's SQL either way
     if (fp.col_index(nm) >= 0)
@@ -387,7 +388,9 @@ void plan_filter(const EvalCall& C, const QueryShape& qs, FilterPlan& fp) {
   // (a tag query's tag may be the value / timestamp column: numeric, it takes the TAGNUM row scan, load_segments)
   if (std::find_if(fp.cols.begin(), fp.cols.end(), [&](const LeafCol& s) {
         return (s.name == kTimestamp || s.name == qs.vcol) && !(qs.tagq && s.name == C.R.tag_name);
-      }) != fp.cols.end())
+      }) != fp.cols.end() ||
+      std::find_if(qs.numgbs.begin(), qs.numgbs.end(), [&](const std::string& g) { return g == kTimestamp || g == qs.vcol; }) !=
+          qs.numgbs.end())
     throw PlanError(LK_ERR_UNSUPPORTED, "filters / groupBys on the timestamp or value column");
   static_cast<LeafNumbering&>(fp) = number_leaves(C.R.filter.get(), qs.all_leaves,
                                                   [](const FilterNode* l) { return numeric_op(l->op); }, qs.nums, fp.cols);
@@ -453,6 +456,61 @@ void load_segments(const EvalCall& C, const QueryShape& qs, GlobPlan& gp) {
     }
 }
 
+namespace {
+// A groupBy that may become a numeric group dimension: not the name, and no string leaf on it (a string leaf keeps
+// the string role: DuckDB's cast of its literal is unpinned, a numeric file empties the glob as before).
+bool numeric_gb_candidate(const EvalCall& C, const QueryShape& qs, const std::string& gb) {
+  if (qs.tagq || gb == kName) return false;
+  return std::none_of(qs.all_leaves.begin(), qs.all_leaves.end(),
+                      [&](const FilterNode* l) { return l->k == gb && !numeric_op(l->op); });
+}
+bool numeric_dim_type(int ptype) { return ptype == pq::BOOLEAN || value_rank(ptype) != 0; }
+}  // namespace
+
+// Numeric group dimensions.  BaseExpr.getChartSql writes `GROUP BY step_ts, "<col>", name`
+// (BaseExpr.scala:338-346, 401-403) and DuckDB groups a BIGINT / DOUBLE / BOOLEAN column like any other, each value
+// printed by JDBC getString (Commons.scala:430-437): a groupBy-only column (or one with gt/ge/lt/le leaves) that some
+// loaded file stores as INT32 / INT64 / FLOAT / DOUBLE / BOOLEAN becomes a numeric query column whose values the row
+// scan discovers (XMODE_NUMDIM) and looks up.  The unions this engine does not restate fail the whole call.
+// (Distributed calls are refused as a whole, agreed on in plan_globs.)
+void plan_numeric_group_bys(const EvalCall& C, QueryShape& qs, const GlobPlan& gp) {
+  if (C.dist) return;
+  for (const std::string& gb : C.R.group_bys) {
+    if (qs.numgb_index(gb) >= 0 || !numeric_gb_candidate(C, qs, gb)) continue;
+    auto refuse = [&](const std::string& why) { throw PlanError(LK_ERR_UNSUPPORTED, "numeric groupBy: column " + gb + " " + why); };
+    bool any_num = false, any_text = false;
+    long text_glob = -1, num_glob = -1;
+    for (size_t i = 0; i < C.n_paths; i += size_t(C.glob_size)) {
+      bool text = false, num = false, boolean = false;
+      for (size_t j = i; j < std::min(C.n_paths, i + size_t(C.glob_size)); j++) {
+        if (!gp.segs[j]) continue;
+        const int c = gp.segs[j]->col_index(gb);
+        if (c < 0) continue;   // absent (NULLs), or of a type the loader does not decode (refused in plan_globs)
+        const HostCol& hc = gp.segs[j]->cols[size_t(c)];
+        if (hc.is_string) text = true;
+        else if (hc.ptype == pq::BOOLEAN) boolean = true;
+        else if (value_rank(hc.ptype)) num = true;
+      }
+      const std::string gs = std::to_string(i / size_t(C.glob_size));
+      // union_by_name of VARCHAR and a number is VARCHAR, the numbers printed by DuckDB's cast; BOOLEAN with a number
+      // does not unify as the numeric classes do
+      if (text && (num || boolean)) refuse("is VARCHAR in some files and numeric in others of glob " + gs);
+      if (boolean && num) refuse("is BOOLEAN in some files and numeric in others of glob " + gs);
+      if (text) any_text = true, text_glob = long(i / size_t(C.glob_size));
+      if (num || boolean) any_num = true, num_glob = long(i / size_t(C.glob_size));
+    }
+    if (!any_num) continue;   // a string groupBy, or a column no loaded file has
+    if (any_text)
+      refuse("is VARCHAR in glob " + std::to_string(text_glob) + " and numeric in glob " + std::to_string(num_glob) + " of the same call");
+    if ((C.flags & kEvalMetricsPct) || (qs.ces && C.R.dataset == "metrics"))
+      refuse("is numeric; metrics p<NN> / ces take no numeric groupBy");
+    if (qs.numgbs.size() >= size_t(MAXND)) refuse("is numeric: more than " + std::to_string(MAXND) + " numeric groupBys");
+    qs.numgbs.push_back(gb);
+    if (std::find(qs.nums.begin(), qs.nums.end(), gb) == qs.nums.end()) qs.nums.push_back(gb);
+    qs.numeric = true;   // every segment takes the general row scan
+  }
+}
+
 void plan_globs(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, GlobPlan& gp) {
   // ---- globs ----
   gp.fset = field_set(C.R);
@@ -474,8 +532,11 @@ void plan_globs(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, G
   const size_t np = gp.probe_cols.size();
   const size_t ng = gp.globs.size();
   // [.. | value NULLs | numeric tag column | globs: a numeric file of the chart field | globs: a VARCHAR file of it]
-  gp.exists.assign(ng * np + 2 * ng + 2 + 2 * ng, 0);
+  // [.. | a numeric groupBy column on some rank (distributed calls: refused, below)]
+  gp.exists.assign(ng * np + 2 * ng + 2 + 2 * ng + 1, 0);
   const size_t vnull_at = ng * np + 2 * ng;
+  const size_t numgb_at = gp.exists.size() - 1;
+  gp.num_ut.assign(qs.numgbs.size(), std::vector<int>(ng, -1));
   gp.exists[vnull_at + 1] = gp.tag_numeric ? 1 : 0;
   uint8_t* gfnum = gp.exists.data() + vnull_at + 2;
   uint8_t* gftext = gfnum + ng;
@@ -572,8 +633,26 @@ void plan_globs(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, G
       }
       for (auto& sc : fp.cols)
         if (bad(sc.name, 2)) gfail[gi] = 1;
-      for (auto& nm : qs.nums)
+      for (auto& nm : qs.nums) {
+        const int k = qs.numgb_index(nm);
+        const int c = k >= 0 ? S.col_index(nm) : -1;
+        if (c >= 0 && numeric_dim_type(S.cols[size_t(c)].ptype) && !S.cols[size_t(c)].is_string) {
+          // the group column's union_by_name type over the glob's files (BOOLEAN alone: plan_numeric_group_bys)
+          const int pt = S.cols[size_t(c)].ptype;
+          int& ut = gp.num_ut[size_t(k)][gi];
+          ut = (ut < 0 || pt == pq::BOOLEAN) ? pt : value_type_of_rank(std::max(value_rank(ut), value_rank(pt)));
+          // a BOOLEAN group column binds; a comparison leaf on it stays a glob failure
+          const bool leafed = std::any_of(qs.all_leaves.begin(), qs.all_leaves.end(), [&](const FilterNode* l) { return l->k == nm; });
+          if (pt == pq::BOOLEAN && !leafed) continue;
+        }
         if (bad(nm, 3)) gfail[gi] = 1;
+      }
+      // distributed: which columns are numeric depends on each rank's segments -- the ranks agree on the refusal
+      if (C.dist)
+        for (auto& gb : fp.gbs) {
+          const int c = numeric_gb_candidate(C, qs, gb) ? S.col_index(gb) : -1;
+          if (c >= 0 && !S.cols[size_t(c)].is_string && numeric_dim_type(S.cols[size_t(c)].ptype)) gp.exists[numgb_at] = 1;
+        }
     }
   // every rank sees every glob's union, failures and value type; a rank-local engine failure fails every rank here
   if (C.dist) comm_agree_max_u8(C.E, C.X, gp.load_err, gp.load_msg, gp.exists.data(), gp.exists.size());
@@ -585,6 +664,11 @@ void plan_globs(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, G
         throw PlanError(LK_ERR_UNSUPPORTED, "field chart: column " + qs.vcol + " is numeric in some files and VARCHAR in others of glob " + std::to_string(gi));
       gp.ftext_any = gp.ftext_any || gftext[gi];
     }
+  if (gp.exists[numgb_at]) {   // (the same text on every rank)
+    std::string names;
+    for (auto& gb : fp.gbs) names += (names.empty() ? "" : ", ") + gb;
+    throw PlanError(LK_ERR_UNSUPPORTED, "numeric groupBy: a distributed evaluation takes no groupBy column stored as a number (groupBys: " + names + ")");
+  }
   gp.tag_numeric = gp.exists[vnull_at + 1] != 0;   // agreed: a numeric tag column on some rank
   if (gp.tag_numeric) return;
   for (size_t gi = 0; gi < ng; gi++)
@@ -651,7 +735,14 @@ void cell_policy(const EvalCall& C, const QueryShape& qs, const GlobPlan& gp, Ce
 }
 
 void plan_dims(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, DimPlan& dp) {
-  dp.dims.assign(fp.cols.size(), DimCol{});
+  dp.dims.assign(fp.cols.size() + qs.numgbs.size(), DimCol{});
+  // numeric group dimensions: sized once the discovery pass has listed their values (eval.cpp: discover_numdims)
+  for (size_t k = 0; k < qs.numgbs.size(); k++) {
+    DimCol& dc = dp.dims[fp.cols.size() + k];
+    dc.is_dim = dc.restricted = dc.numeric = true;
+    dc.ndim = 1;
+    dc.dim_null = 0;
+  }
   for (size_t s = 0; s < fp.cols.size(); s++) {
     const LeafCol& sc = fp.cols[s];
     DimCol& dc = dp.dims[s];
@@ -688,7 +779,12 @@ void plan_dims(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, Di
       dc.dim_null = dc.dict_n;
     }
   }
-  for (int s = int(fp.cols.size()) - 1; s >= 0; s--) {
+  plan_strides(dp);
+}
+
+void plan_strides(DimPlan& dp) {
+  dp.ngroups = 1;
+  for (int s = int(dp.dims.size()) - 1; s >= 0; s--) {
     if (!dp.dims[s].is_dim) continue;
     dp.dims[s].stride = dp.ngroups;
     dp.ngroups *= dp.dims[s].ndim;
@@ -783,7 +879,7 @@ void plan_cells(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, c
     cs.nbuckets = uint64_t((last_b - cs.bucket_base) / gp.step + 1);
   }
   // dims whose null-like values must be folded after per-glob finalization
-  cs.fold_maps.assign(fp.cols.size(), {});
+  cs.fold_maps.assign(dp.dims.size(), {});   // (a numeric dimension's texts are never null-like: no map)
   if (qs.merged && cs.min_max_nulls && !fp.gbs.empty()) {
     for (size_t s = 0; s < fp.cols.size(); s++) {
       const DimCol& dc = dp.dims[s];
@@ -958,6 +1054,8 @@ void plan_segments(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp
         if (want_string != hc.is_string)
           throw PlanError(LK_ERR_DEVICE, "internal: column " + name + " of an unexpected type in a live glob");
         uint32_t pad = uint32_t(hc.ptype);
+        if (const int k = qc >= 2 ? qs.numgb_index(name) : -1; k >= 0)   // a numeric group column: the glob's union type
+          pad |= uint32_t(gp.num_ut[size_t(k)][gi]) << 8;
         if (qc == 0 && hc.ptype != pq::INT64) general = true;   // INT32 timestamps: sign-extended
         if (qc == 1) {
           if (hc.ptype != pq::DOUBLE) general = true;
@@ -1002,6 +1100,7 @@ void plan_segments(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp
       sg.seg_begin.push_back(sg.total_tiles);
       sg.total_tiles += q.ntiles;
       (general ? sg.gsegs : sg.qsegs).push_back(q);
+      if (general) sg.gseg_glob.push_back(uint32_t(gi));
     }
   }
 
@@ -1013,6 +1112,7 @@ void plan_segments(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp
     sg.local_msg = e.what();
     sg.qsegs.clear();
     sg.gsegs.clear();
+    sg.gseg_glob.clear();
     sg.total_tiles = 0;
   }
   for (auto& q : sg.qsegs) sg.max_tiles = std::max(sg.max_tiles, q.ntiles);

@@ -1,6 +1,7 @@
 // Host planning of an aggregate evaluation (eval_plan.cpp): the stages between the parsed request and the first
 // launch, each a function over the structs below.  A stage reads the earlier stages' structs and fills its own.
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <memory>
 #include <mutex>
@@ -29,6 +30,9 @@ constexpr unsigned kEvalDistPerGlob = 1u << 30;
 // epilogue, no key_bits / ts_runs host expansion, no device->host copy.  Off for every C ABI entry point but
 // lk_eval_formula.
 constexpr unsigned kEvalKeepDevice = 1u << 29;
+// internal evaluation flag: the per-glob MAX rows of a metrics `p<NN>` (evaluate_metrics_pct), which takes no numeric
+// groupBy (plan_numeric_group_bys)
+constexpr unsigned kEvalMetricsPct = 1u << 28;
 
 // One evaluation with its re-runs (eval.cpp); the composed evaluations of eval_compose.cpp call it per part.
 int evaluate_req(Engine& E, const std::shared_ptr<const Request>& Rp, const char* const* paths, size_t n_paths,
@@ -66,8 +70,14 @@ struct QueryShape {
   double quantile = 0.0;
   std::string vcol;
   std::vector<const FilterNode*> all_leaves;
-  std::vector<std::string> nums;   // numeric filter columns
+  std::vector<std::string> nums;   // numeric query columns: the filter's, then the numeric groupBys not among them
   bool numeric = false;
+  // groupBys over columns stored as numbers (plan_numeric_group_bys): numeric group dimensions, DESIGN §7.7
+  std::vector<std::string> numgbs;
+  int numgb_index(const std::string& name) const {
+    const auto it = std::find(numgbs.begin(), numgbs.end(), name);
+    return it == numgbs.end() ? -1 : int(it - numgbs.begin());
+  }
 };
 
 // The filter over string columns and numbered leaves, and its truth tables.
@@ -118,6 +128,9 @@ struct GlobPlan {
   std::vector<GlobInfo> globs;
   bool value_nulls = false;
   bool ftext_any = false;     // field chart: some glob's chart field is VARCHAR
+  // numeric groupBys: [numgb][glob] the column's union_by_name type over the glob's files (Parquet type; -1: no file
+  // of the glob has it)
+  std::vector<std::vector<int>> num_ut;
   size_t nfailed = 0;
   int64_t step = -1;
   std::shared_ptr<FieldTab> ftab;
@@ -136,6 +149,7 @@ struct GlobPlan {
 struct DimCol {
   bool is_dim = false;
   bool restricted = false;
+  bool numeric = false;                   // a numeric group dimension: restricted, `cand` = the discovered values' texts
   std::vector<std::string> cand;          // restricted dims: candidate values (dim id = position)
   uint32_t ndim = 1;
   uint32_t dim_null = 0;
@@ -171,8 +185,21 @@ struct CellSpace {
   uint64_t cap = 0, cap_max = 0;   // hash table: first size and bound
 };
 
+// The numeric group dimensions' device tables (eval.cpp: discover_numdims), read by the aggregate scan.
+struct NumDimTables {
+  uint64_t cap = 0;           // slots per (glob, column)
+  int attempts = 0;
+  double ms = 0;
+  unsigned long long* d_keys = nullptr;
+  uint32_t* d_ids = nullptr;
+  uint32_t* d_ones = nullptr;
+  uint32_t* d_flags = nullptr;
+  const uint32_t* d_seg_glob = nullptr;
+};
+
 struct DimPlan {
-  std::vector<DimCol> dims;   // parallel to FilterPlan::cols
+  std::vector<DimCol> dims;   // parallel to FilterPlan::cols, then one per QueryShape::numgbs (least significant)
+  NumDimTables nd;
   uint64_t ngroups = 1;
   double dims_ms = 0;         // distributed group-dim agreement (stats)
   int dims_rebuilt = 0;
@@ -184,6 +211,7 @@ struct DimPlan {
 // Per-segment query descriptors: `qsegs` for the fused kernels, `gsegs` for the general row scan.
 struct SegPlan {
   std::vector<QSeg> qsegs, gsegs;
+  std::vector<uint32_t> gseg_glob;   // the glob of every gseg (QSeg::glob_slot is 0 where globs share cells)
   std::vector<uint32_t> seg_begin;
   uint32_t total_tiles = 0, max_tiles = 0, gmax_tiles = 0;
   uint64_t rows_scanned = 0, alg_bytes = 0;
@@ -202,6 +230,12 @@ struct Plan {
   CellSpace cs;
   DimPlan dp;
   SegPlan sg;
+  // group dimension s (DimPlan::dims): its column, and the dimension of a column
+  const std::string& dim_name(size_t s) const { return s < fp.cols.size() ? fp.cols[s].name : qs.numgbs[s - fp.cols.size()]; }
+  int dim_index(const std::string& name) const {
+    const int k = qs.numgb_index(name);
+    return k >= 0 ? int(fp.cols.size()) + k : fp.col_index(name);
+  }
 };
 
 // The stages, in call order.  shape_gate .. plan_filter read no segment.
@@ -210,9 +244,12 @@ void shape_gate(const EvalCall& C, QueryShape& qs);
 bool answer_without_segments(const EvalCall& C, const QueryShape& qs);
 void plan_filter(const EvalCall& C, const QueryShape& qs, FilterPlan& fp);
 void load_segments(const EvalCall& C, const QueryShape& qs, GlobPlan& gp);
+// Which groupBys are numeric group dimensions (reads the loaded segments' schemas; before plan_filter).
+void plan_numeric_group_bys(const EvalCall& C, QueryShape& qs, const GlobPlan& gp);
 void plan_globs(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, GlobPlan& gp);   // collective: globs
 void cell_policy(const EvalCall& C, const QueryShape& qs, const GlobPlan& gp, CellSpace& cs);
 void plan_dims(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, DimPlan& dp);     // collective: dims
+void plan_strides(DimPlan& dp);   // strides and the group space from the dims' sizes
 void plan_tables(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, const GlobPlan& gp, const CellSpace& cs,
                  DimPlan& dp);
 void plan_cells(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, const GlobPlan& gp, const DimPlan& dp,

@@ -19,7 +19,7 @@ void label_rows(const EvalCall& C, const Plan& pl, uint32_t nrows_out) {
   if (!pl.qs.tagq)
     for (auto& g : C.R.group_bys) {
       C.res->tag_names.push_back(g);
-      col_str.push_back(pl.fp.col_index(g));
+      col_str.push_back(pl.dim_index(g));   // a string column, or a numeric group dimension
     }
   const size_t nreg = C.res->tag_names.size();
   std::vector<std::string> qt_keys;
@@ -34,21 +34,21 @@ void label_rows(const EvalCall& C, const Plan& pl, uint32_t nrows_out) {
   C.res->tcols.resize(nreg);
   for (size_t c = 0; c < nreg; c++) {
     const DimCol& sc = pl.dp.dims[size_t(col_str[c])];
-    const std::string& name = pl.fp.cols[size_t(col_str[c])].name;
+    const std::string& name = pl.dim_name(size_t(col_str[c]));
     lk_result::TagCol& tc = C.res->tcols[c];
     tc.stride = sc.stride ? sc.stride : 1;
     tc.ndim = sc.ndim;
     tc.dim_null = sc.dim_null;
-    {
+    tc.col = name;
+    if (!sc.numeric) {   // (a numeric dimension's strings are this result's own: `local` + `owned` below)
       GlobalDict& gd = C.E.dict(name);
       std::lock_guard<std::mutex> g(gd.mu);
       tc.dict_keep = gd.vals;   // this generation's block stays alive with the result
       tc.dict = tc.dict_keep.get();
+      tc.engine = &C.E;
+      tc.engine_life = C.E.life;
+      tc.dict_n = sc.dict_n;
     }
-    tc.engine = &C.E;
-    tc.engine_life = C.E.life;
-    tc.col = name;
-    tc.dict_n = sc.dict_n;
     if (sc.exchanged) {   // the agreed union's text table, shared (no copy): 10M-value dims cost nothing here
       tc.shared = sc.uni->text;
       tc.keep = sc.uni;

@@ -111,6 +111,36 @@ __device__ void tag_global_add(const XParams& X, uint32_t g, unsigned long long 
 
 constexpr uint32_t TAG_LDS_SLOTS = 512;   // per workgroup (aliases the HIST bins)
 
+// NUMDIM: the bins' LDS as key tables (64-bit keys, no counts), shared evenly among the numeric group columns
+constexpr uint32_t ND_LDS_KEYS = XBINS / 2;
+__device__ __forceinline__ uint32_t nd_lds_slots(uint32_t nnd) { return ND_LDS_KEYS >> (nnd > 2u ? 2u : nnd - 1u); }
+
+// key into (glob g, numeric group column k)'s device table (tag_global_add's probe sequence, keys only)
+__device__ void nd_global_add(const XParams& X, uint32_t g, uint32_t k, unsigned long long key) {
+  const unsigned long long mask = X.ndcap - 1, base = ((unsigned long long)g * X.nnd + k) * X.ndcap;
+  unsigned long long s = tag_hash(key) & mask;
+  for (unsigned long long i = 0; i <= mask && i < 4096; i++, s = (s + 1) & mask) {
+    const unsigned long long prev = atomicCAS(X.ndkeys + base + s, TAG_EMPTY, key);
+    if (prev == TAG_EMPTY || prev == key) return;
+  }
+  atomicOr(X.ndflags, FLAG_HASH_FULL);
+}
+
+// the dim id of `key` in that table (the same probe sequence); false: the table does not hold it
+__device__ __forceinline__ bool nd_lookup(const XParams& X, uint32_t g, uint32_t k, unsigned long long key, uint32_t* id) {
+  const unsigned long long mask = X.ndcap - 1, base = ((unsigned long long)g * X.nnd + k) * X.ndcap;
+  unsigned long long s = tag_hash(key) & mask;
+  for (unsigned long long i = 0; i <= mask && i < 4096; i++, s = (s + 1) & mask) {
+    const unsigned long long have = X.ndkeys[base + s];
+    if (have == key) {
+      *id = X.ndids[base + s];
+      return true;
+    }
+    if (have == TAG_EMPTY) return false;
+  }
+  return false;
+}
+
 }  // namespace
 
 template <int AGG, bool HASH>
@@ -118,7 +148,10 @@ __device__ __forceinline__ void ex_merge(const QParams& q, unsigned long long ce
   global_merge<AGG, HASH>(q, cell, 1u, vok ? 1u : 0u, vok ? v : 0.0, 0.0, vok ? dbl_order(v) : (AGG == AGG_MIN ? ~0ull : 0ull));
 }
 
-__global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
+// NDM 0: HIST / EMIT / TAGNUM / AGG by X.mode.  1: NUMDIM.  2: AGG with numeric group dimensions.  (Instantiations of
+// their own: the numeric-dimension state costs the other modes no register.)
+template <int NDM>
+__device__ __forceinline__ void ex_scan_body(const XParams& X) {
   // column state by query column: 0 timestamp, 1 value (AGG), 2 .. 2+nstr strings, then numeric filter columns
   __shared__ XHot H[MAXQCOL];
   __shared__ LRun vr[MAXQCOL][RUN_CAP];
@@ -131,8 +164,10 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
   const uint32_t t = blockIdx.x;
   if (t >= Sp->ntiles) return;
   const uint32_t g = Sp->glob_slot;
-  const bool aggm = X.mode == XMODE_AGG;
-  const int64_t lo = aggm ? Sp->win_lo : X.rlo[g], hi = aggm ? Sp->win_hi : X.rhi[g];
+  const bool aggm = NDM == 2 || (NDM == 0 && X.mode == XMODE_AGG);
+  const bool swin = aggm || NDM == 1;   // the glob window of the segment descriptor (NUMDIM: the aggregate scan's rows)
+  const uint32_t rg = NDM ? X.seg_glob[blockIdx.y] : 0u;   // the segment's glob, whatever the cell space shares
+  const int64_t lo = swin ? Sp->win_lo : X.rlo[g], hi = swin ? Sp->win_hi : X.rhi[g];
   const TileDesc* tdp = Sp->tiles + t;
   if (lo >= hi || tdp->ts_max < lo || tdp->ts_min >= hi) return;   // zone map outside the glob's open range
   const uint32_t nrows = tdp->nrows;
@@ -143,7 +178,7 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
   if (tid < nc) {
     const int qc = tid;
     XHot h{};
-    h.present = (qc == 1 && !aggm) ? 0u : Sp->cols[qc].present;
+    h.present = (qc == 1 && !aggm && !(NDM == 1 && X.field)) ? 0u : Sp->cols[qc].present;
     if (h.present) {
       const TileCol tc = Sp->cols[qc].tcols[t];
       h.vals = Sp->base + tc.vals;
@@ -164,18 +199,22 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
   }
   if (X.truth)
     for (uint32_t i = tid; i < ((1u << (2 * X.nleaves)) + 31) / 32; i += BLOCK) truth[i] = X.truth[i];
-  if (X.mode == XMODE_HIST)
+  if (NDM == 0 && X.mode == XMODE_HIST)
     for (uint32_t i = tid; i < X.nbins; i += BLOCK) hist[i] = 0;
   // TAGNUM: the workgroup's table in the bins' LDS: [512 keys (u64) | 512 counts | NULL rows | all-ones-key rows]
   unsigned long long* tk = reinterpret_cast<unsigned long long*>(hist);
   uint32_t* tc = hist + 2 * TAG_LDS_SLOTS;
-  if (X.mode == XMODE_TAGNUM) {
+  if (NDM == 0 && X.mode == XMODE_TAGNUM) {
     for (uint32_t i = tid; i < TAG_LDS_SLOTS; i += BLOCK) {
       tk[i] = TAG_EMPTY;
       tc[i] = 0;
     }
     if (tid < 2) tc[TAG_LDS_SLOTS + tid] = 0;
   }
+  // NUMDIM: column k's keys at tk[k * ndl .. + ndl)
+  const uint32_t ndl = NDM == 1 ? nd_lds_slots(X.nnd) : 0u;
+  if (NDM == 1)
+    for (uint32_t i = tid; i < ND_LDS_KEYS; i += BLOCK) tk[i] = TAG_EMPTY;
   __syncthreads();
   for (int qc = 0; qc < nc; qc++) {
     if (!H[qc].present) continue;
@@ -193,13 +232,13 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
   __syncthreads();
 
   const uint32_t leaf_false = Sp->leaf_false;
-  const int64_t hbase = X.mode == XMODE_HIST ? X.hbase[g] : 0;
-  const int64_t hwidth = X.mode == XMODE_HIST ? X.hwidth[g] : 1;
+  const int64_t hbase = (NDM == 0 && X.mode == XMODE_HIST) ? X.hbase[g] : 0;
+  const int64_t hwidth = (NDM == 0 && X.mode == XMODE_HIST) ? X.hwidth[g] : 1;
   uint32_t carry[MAXQCOL];
 #pragma unroll
   for (int k = 0; k < MAXQCOL; k++) carry[k] = 0;
   // field chart over a VARCHAR field: query column 1 holds dictionary codes
-  const bool vtext = aggm && X.field && (Sp->cols[1].pad & VCONV_TEXT);
+  const bool vtext = (aggm || NDM == 1) && X.field && (Sp->cols[1].pad & VCONV_TEXT);
 
   for (uint32_t c0 = 0; c0 < nrows; c0 += BLOCK) {
     const uint32_t r = c0 + uint32_t(tid);
@@ -209,6 +248,8 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
     bool v_def = false;   // the value column's definition level (field charts: a conjunct of the filter)
     uint32_t fgl = 0;     // vtext: the global dictionary id of the row's text
     unsigned long long tag_raw = 0;
+    unsigned long long nd_raw[MAXND] = {};   // NDM: the numeric group columns' raw words
+    bool nd_ok[MAXND] = {};
     int64_t ts = 0;
     double v = 0.0;
     unsigned long long gid = 0;
@@ -250,7 +291,8 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
       }
       if (qc < 2 || qc >= 2 + ns) {   // PLAIN numeric: timestamp, value, numeric filter column
         const bool w8 = h.kind == PAGE_PLAIN64;
-        const bool bl = h.kind == PAGE_BOOL && uint32_t(qc) == X.tag_qc;   // BOOLEAN: a numeric tag only
+        // BOOLEAN: a numeric tag or a numeric group column only
+        const bool bl = h.kind == PAGE_BOOL && (uint32_t(qc) == X.tag_qc || (NDM && ((X.ndmask >> qc) & 1u)));
         if (!w8 && h.kind != PAGE_PLAIN32 && !bl) ok = false;
         // (BOOLEAN: bit-packed bytes read as whole dwords -- the slack keeps the stream's last dword in range)
         const __amdgpu_buffer_rsrc_t rs = make_rsrc(h.vals, h.vals_len + (bl ? 4u : 0u));
@@ -266,6 +308,14 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
         if (uint32_t(qc) == X.tag_qc) {
           tag_raw = raw;
           tag_ok = ok;
+        }
+        if (NDM) {
+#pragma unroll
+          for (int k = 0; k < MAXND; k++)
+            if (k < int(X.nnd) && uint32_t(qc) == X.nd[k].qc) {
+              nd_raw[k] = raw;
+              nd_ok[k] = ok;
+            }
         }
         if (qc == 0) {   // BIGINT over INT64 / INT32 files (union_by_name)
           ts = w8 ? int64_t(raw) : int64_t(int32_t(uint32_t(raw)));
@@ -285,7 +335,7 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
           v_ok = ok;
           v_def = ok;
         } else {
-          const uint32_t pt = Sp->cols[qc].pad;   // Parquet physical type of this segment's column
+          const uint32_t pt = Sp->cols[qc].pad & 0xffu;   // Parquet physical type of this segment's column
           const bool is_int = pt == 1u || pt == 2u;
           const long long iv = pt == 2u ? (long long)raw : (long long)int32_t(uint32_t(raw));
           const double dv = pt == 5u ? __longlong_as_double((long long)raw) : double(__uint_as_float(uint32_t(raw)));
@@ -340,7 +390,40 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
       pass = x_interpret(X, T, F);
     }
     pass = pass && ts_ok && ts >= lo && ts < hi;
-    if (X.mode == XMODE_AGG) {
+    if (NDM == 1) {
+      // every row the aggregate scan will merge: per numeric group column its canonical key, deduplicated across the
+      // wave (one leader per distinct key) into the workgroup's LDS table; the all-ones key into the column's flag word
+      if (X.field) pass = pass && v_def;
+#pragma unroll
+      for (int k = 0; k < MAXND; k++) {
+        if (k >= int(X.nnd)) break;
+        const bool has = pass && nd_ok[k];
+        const unsigned long long key = has ? tag_key(nd_raw[k], Sp->cols[X.nd[k].qc].pad) : 0ull;
+        const unsigned long long mo = __ballot(has && key == TAG_EMPTY);
+        if (lane == 0 && mo) atomicOr(X.ndones + size_t(rg) * X.nnd + k, 1u);
+        unsigned long long act = __ballot(has && key != TAG_EMPTY);
+        unsigned long long* tkk = tk + uint32_t(k) * ndl;
+        while (act) {
+          const int leader = __ffsll((long long)act) - 1;
+          const uint32_t lo32 = __shfl(uint32_t(key), leader), hi32 = __shfl(uint32_t(key >> 32), leader);
+          const unsigned long long lk = (unsigned long long)hi32 << 32 | lo32;
+          const unsigned long long m = __ballot(has && key == lk);
+          if (lane == leader) {
+            uint32_t s = uint32_t(tag_hash(lk)) & (ndl - 1);
+            bool done = false;
+            for (uint32_t i = 0; i < ndl; i++, s = (s + 1) & (ndl - 1)) {
+              const unsigned long long prev = atomicCAS(&tkk[s], TAG_EMPTY, lk);
+              if (prev == TAG_EMPTY || prev == lk) {
+                done = true;
+                break;
+              }
+            }
+            if (!done) nd_global_add(X, rg, uint32_t(k), lk);   // the workgroup's table is full
+          }
+          act &= ~m;
+        }
+      }
+    } else if (aggm) {
       if (X.field) pass = pass && v_def;   // `<field> IS NOT NULL`
       if (pass && vtext) {
         v = X.ftab[fgl];
@@ -350,7 +433,26 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
         const QParams& q = X.q;
         int64_t b;
         bool ok = true;
-        if (q.metrics) {   // BaseExpr.scala:376-394: the raw timestamp, on the step grid
+        if (NDM == 2) {   // numeric group columns: the dim id the discovery pass gave the row's key
+#pragma unroll
+          for (int k = 0; k < MAXND; k++) {
+            if (k >= int(X.nnd)) break;
+            uint32_t id = X.nd[k].dim_null;   // NULL / absent
+            if (nd_ok[k]) {
+              const unsigned long long key = tag_key(nd_raw[k], Sp->cols[X.nd[k].qc].pad);
+              if (key == TAG_EMPTY) {
+                id = X.ndones[size_t(rg) * X.nnd + k];
+              } else if (!nd_lookup(X, rg, uint32_t(k), key, &id)) {
+                atomicOr(q.flags, FLAG_NUMDIM_MISS);   // the discovery ran over the same rows
+                ok = false;
+              }
+            }
+            gid += (unsigned long long)id * X.nd[k].dim_stride;
+          }
+        }
+        if (!ok) {
+          b = 0;   // (flagged above)
+        } else if (q.metrics) {   // BaseExpr.scala:376-394: the raw timestamp, on the step grid
           const int64_t d = ts - q.bucket_base;
           b = d / q.step;
           if (d - b * q.step != 0) {
@@ -380,7 +482,7 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
           }
         }
       }
-    } else if (X.mode == XMODE_TAGNUM) {
+    } else if (NDM == 0 && X.mode == XMODE_TAGNUM) {
       // every passing row of the glob window: NULL tags and the all-ones key counted apart; the other keys deduplicated
       // across the wave (one leader per distinct key) and added into the workgroup's LDS table
       const int cls = !pass ? 0 : (!tag_ok ? 2 : 1);
@@ -411,13 +513,13 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
         }
         act &= ~m;
       }
-    } else if (X.mode == XMODE_HIST) {
+    } else if (NDM == 0 && X.mode == XMODE_HIST) {
       if (pass) {
         int64_t b = (ts - hbase) / hwidth;
         b = b < 0 ? 0 : (b >= int64_t(X.nbins) ? int64_t(X.nbins) - 1 : b);
         atomicAdd(&hist[b], 1u);
       }
-    } else {
+    } else if (NDM == 0) {
       const unsigned long long m = __ballot(pass);
       if (m) {
         uint32_t base = 0;
@@ -430,18 +532,27 @@ __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) {
       }
     }
   }
-  if (X.mode == XMODE_HIST) {
+  if (NDM == 1) {   // flush: one device CAS per distinct key of the tile
+    __syncthreads();
+    for (uint32_t i = tid; i < ND_LDS_KEYS; i += BLOCK)
+      if (i / ndl < X.nnd && tk[i] != TAG_EMPTY) nd_global_add(X, rg, i / ndl, tk[i]);
+  }
+  if (NDM == 0 && X.mode == XMODE_HIST) {
     __syncthreads();
     for (uint32_t i = tid; i < X.nbins; i += BLOCK)
       if (hist[i]) atomicAdd(&X.hist[size_t(g) * X.nbins + i], hist[i]);
   }
-  if (X.mode == XMODE_TAGNUM) {   // flush: one device atomic per distinct key of the tile
+  if (NDM == 0 && X.mode == XMODE_TAGNUM) {   // flush: one device atomic per distinct key of the tile
     __syncthreads();
     for (uint32_t i = tid; i < TAG_LDS_SLOTS; i += BLOCK)
       if (tk[i] != TAG_EMPTY) tag_global_add(X, g, tk[i], tc[i]);
     if (tid < 2 && tc[TAG_LDS_SLOTS + tid]) atomicAdd(X.tspec + 2 * size_t(g) + tid, (unsigned long long)tc[TAG_LDS_SLOTS + tid]);
   }
 }
+
+__global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) { ex_scan_body<0>(X); }
+__global__ __launch_bounds__(BLOCK) void ex_scan_discover(XParams X) { ex_scan_body<1>(X); }
+__global__ __launch_bounds__(BLOCK) void ex_scan_numdim(XParams X) { ex_scan_body<2>(X); }
 
 __global__ __launch_bounds__(256) void tag_compact(const unsigned long long* keys, const unsigned long long* cnt,
                                                    unsigned long long n, unsigned long long tcap,
@@ -565,6 +676,22 @@ __global__ __launch_bounds__(256) void ex_gather(GParams G) {
 hipError_t launch_ex_scan(const XParams& X, hipStream_t stream) {
   if (!X.nsegs || !X.max_tiles) return hipSuccess;
   hipLaunchKernelGGL(ex_scan, dim3(X.max_tiles, X.nsegs), dim3(BLOCK), 0, stream, X);
+  return hipGetLastError();
+}
+
+hipError_t launch_ex_scan_numdim(const XParams& X, hipStream_t stream) {
+  if (!X.nsegs || !X.max_tiles) return hipSuccess;
+  if (!X.nnd || X.nnd > uint32_t(MAXND) || !X.ndcap || (X.ndcap & (X.ndcap - 1)) || !X.seg_glob || !X.ndkeys || !X.ndones)
+    return hipErrorInvalidValue;
+  if (X.mode == XMODE_NUMDIM) {
+    if (!X.ndflags) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ex_scan_discover, dim3(X.max_tiles, X.nsegs), dim3(BLOCK), 0, stream, X);
+  } else if (X.mode == XMODE_AGG) {
+    if (!X.ndids) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ex_scan_numdim, dim3(X.max_tiles, X.nsegs), dim3(BLOCK), 0, stream, X);
+  } else {
+    return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

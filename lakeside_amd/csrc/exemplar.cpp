@@ -77,8 +77,10 @@ int union_type(int a, int b) {
   return pq::FLOAT;
 }
 
+}  // namespace
+
 // A raw 64-bit word of Parquet physical type `ptype` as a double: DOUBLE / FLOAT bit patterns, INT32 / INT64 values.
-double raw_as_double(unsigned long long raw, int ptype) {
+static double raw_as_double(unsigned long long raw, int ptype) {
   switch (ptype) {
     case pq::DOUBLE: {
       double d;
@@ -117,6 +119,14 @@ std::string value_text(unsigned long long raw, int pt, int ut) {
   }
 }
 
+// A test knob of the environment, read on every call (the tests change them between the calls of one process).
+uint64_t env_u64(const char* name, uint64_t dflt, uint64_t floor) {
+  const char* e = getenv(name);
+  return e ? std::max<uint64_t>(floor, strtoull(e, nullptr, 10)) : dflt;
+}
+
+namespace {
+
 // Rows summed per key, in first-seen order: the first row of a key is kept and `add` folds the later ones into it.
 template <class Row, class Key, class Add>
 std::vector<Row> sum_first_seen(std::vector<Row>& rows, Key key, Add add) {
@@ -128,12 +138,6 @@ std::vector<Row> sum_first_seen(std::vector<Row>& rows, Key key, Add add) {
     else add(out[it->second], r);
   }
   return out;
-}
-
-// A test knob of the environment, read on every call (the tests change them between the calls of one process).
-uint64_t env_u64(const char* name, uint64_t dflt, uint64_t floor) {
-  const char* e = getenv(name);
-  return e ? std::max<uint64_t>(floor, strtoull(e, nullptr, 10)) : dflt;
 }
 
 // A pinned host block from the engine's pool for the length of a transfer (returned to the pool on scope exit).

@@ -127,13 +127,29 @@ hipError_t launch_sparse_write(const SParams& S, unsigned long long n, void* ws,
 // every tile meeting its glob's open range [rlo, rhi) and either counts passing rows per time bin (HIST) or appends
 // them as (timestamp, segment << 48 | tile << 16 | row) records (EMIT).
 constexpr uint32_t XBINS = 2048;
-enum XMode : uint32_t { XMODE_HIST = 0, XMODE_EMIT = 1, XMODE_AGG = 2, XMODE_TAGNUM = 3 };
+enum XMode : uint32_t { XMODE_HIST = 0, XMODE_EMIT = 1, XMODE_AGG = 2, XMODE_TAGNUM = 3, XMODE_NUMDIM = 4 };
 // XMODE_TAGNUM (tag queries over a numeric tag column): passing rows counted per (glob, canonical tag value) in a
 // per-glob open-addressing table (wave dedup -> LDS table -> device atomics); NULL tags and the one value whose
 // canonical key is the empty marker (all ones) are counted apart.  NumLeaf.pad bit 1 (NUMLEAF_NOTNULL): the leaf is
 // `IS NOT NULL` on that column (query-api's `exists` on the tag).
 constexpr uint32_t NUMLEAF_NOTNULL = 2u;
 constexpr unsigned long long TAG_EMPTY = ~0ull;
+// Numeric group dimensions (a groupBy over an INT32 / INT64 / FLOAT / DOUBLE / BOOLEAN column): the column
+// is a numeric query column whose QCol.pad carries the glob's union type (Parquet type | union type << 8, as TAGNUM).
+// XMODE_NUMDIM (the discovery pass, before the aggregate scan): every row that passes the filter and the glob window
+// puts the canonical key of each numeric group column into that (glob, column)'s open-addressing table of ndcap slots
+// (wave dedup -> LDS table -> one device CAS per distinct key per tile); the all-ones key, which is the empty marker,
+// sets the (glob, column)'s word of ndones instead.  XMODE_AGG with nnd != 0 (ex_scan_numdim): a passing row probes
+// the same table and adds ndids[slot] * dim_stride to its group id (ndones then holds the all-ones key's dim id); a
+// key the table does not hold raises FLAG_NUMDIM_MISS.
+constexpr int MAXND = 4;
+constexpr uint32_t FLAG_NUMDIM_MISS = 64u;   // beside layout.hpp's Flag bits, in QParams::flags
+struct NumDim {
+  uint32_t qc;                     // query column
+  uint32_t dim_stride;
+  uint32_t dim_null;               // dim id of NULL / absent
+  uint32_t pad;
+};
 // A numeric comparison leaf (`gt/ge/lt/le`, BaseExpr.scala:488-498) on numeric filter column `col` (QSeg column
 // 2 + nstr + col, its Parquet physical type in QCol.pad): TRUE iff the value lies in the interval, FALSE otherwise,
 // UNKNOWN on NULL.  Integer columns test [ilo, ihi] (exact); floating columns the double interval, NaN (ordered
@@ -188,11 +204,23 @@ struct XParams {
   unsigned long long* tcnt;
   unsigned long long* tspec;
   uint32_t* tflags;
+  // numeric group dimensions (NUMDIM, and AGG through ex_scan_numdim): tables [glob][nnd][ndcap]
+  uint32_t nnd;
+  uint32_t ndmask;                 // bit qc: query column qc is a numeric group column (BOOLEAN pages decode)
+  NumDim nd[MAXND];
+  const uint32_t* seg_glob;        // [nsegs]: the segment's glob (QSeg::glob_slot is 0 where globs share cells)
+  unsigned long long ndcap;
+  unsigned long long* ndkeys;      // TAG_EMPTY-initialised
+  const uint32_t* ndids;           // AGG: dim id per slot
+  uint32_t* ndones;                // [glob][nnd]: NUMDIM: all-ones key seen; AGG: its dim id
+  uint32_t* ndflags;               // NUMDIM: FLAG_HASH_FULL
 };
 // TAGNUM tables -> records [key, count, glob] of the occupied slots (unordered); count at *out_n.
 hipError_t launch_tag_compact(const unsigned long long* keys, const unsigned long long* cnt, unsigned long long tcap,
                               uint32_t nglobs, unsigned long long* out, uint32_t* out_n, hipStream_t stream);
 hipError_t launch_ex_scan(const XParams& X, hipStream_t stream);
+// XMODE_NUMDIM, or XMODE_AGG with numeric group dimensions: instantiations of their own, so ex_scan's registers stay
+hipError_t launch_ex_scan_numdim(const XParams& X, hipStream_t stream);
 
 struct GCol {                      // one (segment, output column) of an exemplar gather
   const uint8_t* base;             // segment streams
