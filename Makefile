@@ -22,7 +22,7 @@ HIP_OBJS  = $(OBJDIR)/kernels.o $(OBJDIR)/ex_kernels.o $(OBJDIR)/formula_kernels
 HDRS = $(wildcard $(SRC)/*.hpp) $(SRC)/unicode_tables.inc include/lakeside_gpu.h include/lakeside_regex.h include/lakeside_text.h
 # device code includes only these (host-only header edits do not rebuild the kernels); lean_kernel.hpp only the
 # scan_lean units, scan_kernel.hpp only the scan units
-DEV_HDRS = $(SRC)/device_common.hpp $(SRC)/kernels.hpp $(SRC)/layout.hpp $(SRC)/scan_inst.hpp
+DEV_HDRS = $(SRC)/device_common.hpp $(SRC)/kernels.hpp $(SRC)/layout.hpp $(SRC)/scan_inst.hpp $(SRC)/bucket.hpp
 # the formula kernels: correctly rounded IEEE double, one operation at a time (no contraction; they use no atomics on
 # floating point, so -munsafe-fp-atomics selects nothing in this unit)
 $(OBJDIR)/formula_kernels.o: HIPFLAGS += -ffp-contract=off
@@ -50,8 +50,8 @@ $(RELIB): $(SRC)/regex.cpp $(SRC)/regex_capi.cpp $(SRC)/regex.hpp $(SRC)/unicode
 
 # host-only Java 17 number text, the field charts' text -> double classifier and the formula parser / cell function
 # (CPU differential tests)
-$(TXLIB): $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/ex_select_sim.cpp $(SRC)/formula.hpp $(SRC)/formula_cell.hpp $(SRC)/evalutil.hpp $(SRC)/ex_select.hpp $(SRC)/kernels.hpp include/lakeside_text.h
-	g++ $(CXXFLAGS_HOST) -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -shared -o $@ $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/ex_select_sim.cpp
+$(TXLIB): $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/ex_select_sim.cpp $(SRC)/bucket_sim.cpp $(SRC)/formula.hpp $(SRC)/formula_cell.hpp $(SRC)/evalutil.hpp $(SRC)/ex_select.hpp $(SRC)/bucket.hpp $(SRC)/kernels.hpp include/lakeside_text.h
+	g++ $(CXXFLAGS_HOST) -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -shared -o $@ $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/ex_select_sim.cpp $(SRC)/bucket_sim.cpp
 
 $(SYNTH): tools/synth.cpp $(SRC)/thrift.hpp
 	g++ -O3 -std=c++17 -fPIC -shared -pthread -Wall -o $@ tools/synth.cpp
@@ -76,7 +76,7 @@ $(CPULIB): oracle/cpu/lkcpu.cpp
 all: $(CPULIB)
 
 # Kernel A/B builds (experiments): the library with the scan kernels built under EXP_FLAGS (e.g.
-# EXP_FLAGS=-DLK_LEAN_ROWS=4 EXP_NAME=rows4; the scan_lean units only) -> lakeside_amd/exp/liblakeside_gpu_<EXP_NAME>.so,
+# EXP_FLAGS=-O2 EXP_NAME=o2, or a -D a local experiment reads; the scan_lean units only) -> lakeside_amd/exp/liblakeside_gpu_<EXP_NAME>.so,
 # selected with LK_LIB_PATH.
 EXP_FLAGS ?=
 EXP_NAME ?= x

@@ -43,6 +43,13 @@ int lk_ex_select_sim(const int64_t* ts, size_t n, int64_t win_lo, int64_t win_hi
                      uint64_t limit, int desc, uint64_t cand_cap, uint64_t probe_rows,
                      int64_t* elo, int64_t* ehi, uint64_t* count, int* passes);
 
+/* Runs the row -> bucket rule the scan kernels inline (lakeside_amd/csrc/bucket.hpp) over ts[0..n): bucket_row with the
+ * window [win_lo, win_hi), inv_step = 1.0 / step as the evaluator sets it, and fast_div as given (the caller keeps to
+ * its domain, 0 <= ts - base < 2^32 and step < 2^31) into bucket[i] / status[i] (0 inside, 1 outside the window,
+ * 2 metrics-unaligned, 3 out of range; the bucket of an outside row is unspecified), and bucket_mono into mono[i]. */
+void lk_bucket_sim(const int64_t* ts, size_t n, int64_t win_lo, int64_t win_hi, int64_t step, int64_t base,
+                   uint64_t nbuckets, int metrics, int fast_div, int64_t* bucket, uint8_t* status, int64_t* mono);
+
 #ifdef __cplusplus
 }
 #endif

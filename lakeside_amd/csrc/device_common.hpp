@@ -1,4 +1,4 @@
-// Device helpers shared by the HIP kernels (included by kernels.hip only).
+// Device helpers shared by the HIP kernels (kernels.hip, ex_kernels.hip and, through scan_inst.hpp, the scan units).
 #pragma once
 #include <hip/hip_runtime.h>
 

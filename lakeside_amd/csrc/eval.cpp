@@ -320,14 +320,7 @@ void setup_scan(const EvalCall& C, const Plan& pl, DevState& dv) {
     bool late_leaves = false;
     for (size_t s = 0; s < pl.fp.cols.size(); s++)
       if (((pl.fp.late_mask >> pl.fp.dev_of[s]) & 1u) && !pl.fp.cols[s].leaves.empty()) late_leaves = true;
-    // tag queries: COUNT(*) counted in the chunk loop from the late window (A/B: LK_TAG_DIRECT=1)
-    const bool tag_direct = pl.qs.tagq && getenv("LK_TAG_DIRECT") && *getenv("LK_TAG_DIRECT") == '1';
-    dv.P.late_chunk = ((late_leaves || tag_direct) && pl.dp.ngroups <= 65536u && (getenv("LK_LATE_CHUNK") || tag_direct)) ? 1u : 0u;
-    // speculative value gather for late-filtered rows (lean_kernel.hpp rowsN): opt-in
-    // (LK_SPEC_GATHER=1) -- measured slower on C3, 2.155 vs 1.968 ms: the loads of the rows the late filter drops
-    // (half of C3's listed rows) cost more than the round trip they save (profiles/r05_bench_c3*.json)
-    const char* sg = getenv("LK_SPEC_GATHER");
-    dv.P.spec_gather = (late_leaves && sg && *sg == '1') ? 1u : 0u;
+    dv.P.late_chunk = (late_leaves && pl.dp.ngroups <= 65536u && getenv("LK_LATE_CHUNK")) ? 1u : 0u;
     // one string column whose eq / in filter passes a quarter or more of its values (the dense query): the 5-wave
     // per-lane scan_lean<..., 0, EARLY> -- its dense-code tiles lose ~0.3 ms in C2's 4-wave listed shape
     // (LK_NO_DENSE_SHAPE=1: A/B).  Against the dictionary's live ids (values some cached segment references), not

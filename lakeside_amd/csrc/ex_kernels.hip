@@ -20,6 +20,7 @@
 
 #include <cstdint>
 
+#include "bucket.hpp"
 #include "device_common.hpp"
 #include "kernels.hpp"
 #include "layout.hpp"
@@ -452,19 +453,13 @@ __device__ __forceinline__ void ex_scan_body(const XParams& X) {
         }
         if (!ok) {
           b = 0;   // (flagged above)
-        } else if (q.metrics) {   // BaseExpr.scala:376-394: the raw timestamp, on the step grid
-          const int64_t d = ts - q.bucket_base;
-          b = d / q.step;
-          if (d - b * q.step != 0) {
-            atomicOr(q.flags, FLAG_METRICS_UNALIGNED);
-            ok = false;
-          }
-        } else {           // BaseExpr.scala:163-165: ts - ts % step
-          b = ((ts - ts % q.step) - q.bucket_base) / q.step;
-        }
-        if (ok && (b < 0 || (uint64_t)b >= q.nbuckets)) {
-          atomicOr(q.flags, FLAG_CELL_RANGE);
-          ok = false;
+        } else {   // the per-row rule (bucket.hpp), exact division; `pass` holds its window test already
+          __builtin_assume(ts >= lo && ts < hi);
+          const RowBucket rb = bucket_row(ts, lo, hi, BucketRule{q.step, q.bucket_base, q.nbuckets, 0.0, q.metrics != 0, false});
+          b = rb.b;
+          if (rb.st == BUCKET_UNALIGNED) atomicOr(q.flags, FLAG_METRICS_UNALIGNED);
+          if (rb.st == BUCKET_RANGE) atomicOr(q.flags, FLAG_CELL_RANGE);
+          ok = rb.st == BUCKET_IN;
         }
         if (ok) {
           unsigned long long cell = ((unsigned long long)g * q.nbuckets + (unsigned long long)b) * q.ngroups + gid;

@@ -194,10 +194,9 @@ struct QParams {
   uint32_t dir_planes;
   uint32_t dir_rep;                  // replicas per direct-table cell (1, 2 or 4)
   uint32_t rows_only;                // COUNT(*) (tag queries): no value column bound; lean tiles take none
-  uint32_t late_chunk;               // scan_lean NL > 0: late columns decoded per 16-row chunk in the main loop (the
-                                     // list then carries each row's group term; lean_kernel.hpp)
-  uint32_t spec_gather;              // scan_lean NL > 0 with a late filter: a listed row's timestamp / value loads go
-                                     // out with its late-column loads, before the late filter decides (lean_kernel.hpp)
+  uint32_t late_chunk;               // scan_lean<..., EARLY>.  NL > 0: late columns decoded per 16-row chunk in the main
+                                     // loop (the list then carries each row's group term); NL = 0: the dense-code
+                                     // shape (lean_kernel.hpp, LeanShape)
   // SUM over integral values (every segment's value column: integers of magnitude <= M, load-time summary) whose
   // rows x M < 2^53: every partial sum is exact in any order, so the TwoSum compensation (and the old value a
   // returning atomic fetches for it) is dropped -- adds are fire-and-forget; results are identical

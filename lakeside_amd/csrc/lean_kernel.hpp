@@ -21,6 +21,7 @@
 #pragma once
 #include <type_traits>
 
+#include "bucket.hpp"
 #include "device_common.hpp"
 
 namespace lk {
@@ -31,86 +32,53 @@ constexpr uint32_t LEAN_LINES = (TILE_ROWS * 8 / 128 + 2 + 31) / 32;   // plan b
 constexpr uint32_t LEAN_LLINES = (TILE_ROWS * 4 / 128 + 2 + 31) / 32;  // plan bytes: late stream lines (bw <= 32)
 constexpr uint32_t LEAN_SPLIT_MAX = 4;   // split tiles: class boundaries (the tile's bucket span + 1) at most
 
-#ifndef LK_LEAN_LIST
-#define LK_LEAN_LIST 512
-#endif
-constexpr uint32_t LEAN_LIST = LK_LEAN_LIST;                           // per-wave list of passing rows (late columns)
-#ifndef LK_LEAN_ROWS
-#define LK_LEAN_ROWS 2
-#endif
-#ifndef LK_LEAN_WAVES2
-#define LK_LEAN_WAVES2 4
-#endif
-#ifndef LK_LEAN_WAVES1
-#define LK_LEAN_WAVES1 5
-#endif
-// NL = 0 with a value gather (C2): passing rows through the wave's LDS list too -- a trip of 128 rows with every lane
-// busy per round trip -- instead of each lane looping over its own chunk's passing rows two at a time (a round then
-// lasts as many round trips as its busiest lane); built for 4 waves per SIMD with 2 chunk rounds in flight: C2 1.27 ->
-// 1.08 ms, C2 at a 10 s step 1.40 -> 1.18 ms (A/B: -DLK_LEAN_LIST0=0).  Dense-code tiles (a quarter or more of the
-// codes pass: the dense query) keep the per-lane loop and its row-major dense blocks.
-#ifndef LK_LEAN_LIST0
-#define LK_LEAN_LIST0 1
-#endif
-#ifndef LK_LEAN_WAVES0V
-#define LK_LEAN_WAVES0V 4
-#endif
-// one late column with a value gather (C4 / C5: SUM / MIN / MAX): 4 waves per SIMD and 3 chunk loads in flight measured
-// faster than 5 waves with one (C4 1.59 -> 1.47 ms); COUNT(*) (tag queries, no gather) keeps 5 waves (A/B: -DLK_LEAN_WAVES1V)
-#ifndef LK_LEAN_WAVES1V
-#define LK_LEAN_WAVES1V 4
-#endif
-#ifndef LK_LEAN_PF1V
-#define LK_LEAN_PF1V 3
-#endif
-// chunk loads in flight ahead of the round, by late-column count (A/B: -DLK_LEAN_PF0 / 1 / 2); the 5-wave shapes
-// (NL <= 1, 96 VGPRs) keep their register budget, the 4-wave NL = 2 shape has room for a deeper ring
-#ifndef LK_LEAN_PF0
-#define LK_LEAN_PF0 (LK_LEAN_LIST0 ? 2 : 0)
-#endif
-#ifndef LK_LEAN_PF0E
-#define LK_LEAN_PF0E 0   // NL = 0 dense-code shape (EARLY): chunk loads in the round itself
-#endif
-#ifndef LK_LEAN_PF0C
-#define LK_LEAN_PF0C 2   // NL = 0 COUNT (no value gather): 0.857 -> 0.754 ms on `count` with 2 rounds in flight
-#endif
-#ifndef LK_LEAN_PF1
-#define LK_LEAN_PF1 1
-#endif
-// unrotated chunk ring (A/B: -DLK_LEAN_SLOTS=0, the rotated ring of r02-r06): see the main loop
-#ifndef LK_LEAN_SLOTS
-#define LK_LEAN_SLOTS 1
-#endif
-// deferred trips of the late-column shapes (opt-in A/B: -DLK_LEAN_DEFER=1): see list_trip.  The pending trip's
-// registers (rows, group terms, late words) live across the chunk rounds, so these shapes run a shallower chunk ring
-// (LK_LEAN_PF1D / LK_LEAN_PF2D) and the COUNT(*) one 4 waves per SIMD (LK_LEAN_WAVES1D).  Measured (r06, validated):
-// tag 0.970 -> 1.161 ms, C4 1.352 -> 1.357, C3 1.786 -> 1.784, with a 2-deep ring C4 1.409, C3 1.820 -- the other
-// waves on the SIMD already hide the trip's first round trip, and the shallower ring / fewer waves cost more than
-// the overlap buys (profiles/r06_ab_defer_*.json)
-#ifndef LK_LEAN_DEFER
-#define LK_LEAN_DEFER 0
-#endif
-#define LEAN_DEFER(NL, AGG) (LK_LEAN_DEFER && (NL) > 0)
-#ifndef LK_LEAN_PF1D
-#define LK_LEAN_PF1D 1
-#endif
-#ifndef LK_LEAN_PF2D
-#define LK_LEAN_PF2D 1
-#endif
-#ifndef LK_LEAN_WAVES1D
-#define LK_LEAN_WAVES1D 4
-#endif
-#ifndef LK_LEAN_PF2
-#define LK_LEAN_PF2 3
-#endif
-// waves per SIMD the kernel is built for (A/B: -DLK_LEAN_WAVES1 / -DLK_LEAN_WAVES2)
-#define LEAN_WAVES(NL, AGG) ((NL) == 0 ? ((AGG) == AGG_COUNT || !LK_LEAN_LIST0 ? LK_LEAN_WAVES1 : LK_LEAN_WAVES0V) \
-                                      : (NL) == 1 ? ((AGG) == AGG_COUNT ? (LEAN_DEFER(NL, AGG) ? LK_LEAN_WAVES1D : LK_LEAN_WAVES1) \
-                                                                        : LK_LEAN_WAVES1V) : LK_LEAN_WAVES2)
-constexpr int LEAN_ROWS = LK_LEAN_ROWS;                                // listed rows per lane per trip (A/B: -DLK_LEAN_ROWS)
+constexpr uint32_t LEAN_LIST = 512;                                    // per-wave list of passing rows (a ring)
+constexpr int LEAN_ROWS = 2;                                           // listed rows per lane per trip
 constexpr uint32_t LEAN_TRIP = 64u * LEAN_ROWS;                        // listed rows per trip
 // the per-wave list is a ring indexed with & (LEAN_LIST - 1) and drained LEAN_TRIP rows at a time
-static_assert((LEAN_LIST & (LEAN_LIST - 1u)) == 0u && LEAN_TRIP <= LEAN_LIST, "LK_LEAN_LIST / LK_LEAN_ROWS");
+static_assert((LEAN_LIST & (LEAN_LIST - 1u)) == 0u && LEAN_TRIP <= LEAN_LIST, "LEAN_LIST / LEAN_ROWS");
+
+// What each scan_lean<AGG, HASH, NL, EARLY> instantiation is built as.  The numbers were chosen by A/B on the bench
+// queries (DESIGN §3 "Shapes", §6); the variants that lost are not in the code any more.
+//
+//   <NL, EARLY>  AGG     waves  PF  ring     rows            serves                    measured
+//   <0, false>   COUNT   5      2   slots    no-load count   `count`                   0.857 -> 0.754 ms (2 rounds in flight),
+//                                                                                      0.733 -> 0.476 ms (slots, load-free rows)
+//   <0, false>   value   4      2   slots    listed (LIST0)  C2, c2s10, c2shuf, gt     C2 1.27 -> 1.08 ms, c2s10 1.40 -> 1.18 ms
+//   <0, true>    COUNT   5      0   -        no-load count   dense filter, COUNT       the dense shape below, no gather
+//   <0, true>    value   5      0   -        per-lane loop,  `dense` (a quarter or     2.70 -> 2.39 ms against the listed
+//                                            dense blocks    more of the names pass)   4-wave shape (r05)
+//   <1, false>   COUNT   5      1   rotated  listed          `tag` (COUNT(*))          0.96 ms at 5 waves (96 VGPRs) vs 1.14 at 4;
+//                                                                                      a deeper ring: no change; no split tiles
+//   <1, false>   value   4      3   rotated  listed          C4, c4real, C5            C4 1.59 -> 1.47 ms vs 5 waves, 1 in flight
+//   <2, false>   any     4      3   rotated  listed, half    C3                        5 waves: no change; 3 waves 2.19 ms; slots
+//                                            ring                                      1.80 -> 1.86 ms (spills)
+//   <1|2, true>  any     4      as above,    listed after    LK_LATE_CHUNK=1 (opt-in)  C3 3.47 vs 1.96 ms, tag 2.28 vs 1.06 ms:
+//                               rotated      the late filter                           slower, kept for its test
+//
+// "slots": round j consumes ring slot j % PF and refills it after its last use, the rounds unrolled PF at a time;
+// "rotated": x = xr[0]; xr[i] = xr[i + 1] (see the main loop for why each shape has the ring it has).
+template <int AGG, int NL, bool EARLY>
+struct LeanShape {
+  static constexpr bool COUNT = AGG == AGG_COUNT;
+  // waves per SIMD the kernel is built for (amdgpu_waves_per_eu)
+  static constexpr int WAVES = EARLY ? (NL == 0 ? 5 : 4) : (NL <= 1 && COUNT ? 5 : 4);
+  // chunk loads in flight ahead of the round (0: loaded in the round itself)
+  static constexpr int PF = NL == 0 ? (EARLY ? 0 : 2) : (NL == 1 && COUNT ? 1 : 3);
+  // rotated ring: the late-column shapes (their early-late bodies are among them: that body exists only for NL > 0,
+  // so it adds no case of its own)
+  static constexpr bool ROT = NL > 0;
+  // NL = 0 with a value gather outside the dense shape lists its passing rows like the late-column shapes
+  static constexpr bool LIST0 = NL == 0 && !COUNT && !EARLY;
+  static constexpr bool LISTED = NL > 0 || LIST0;                      // holds the per-wave list ring in LDS
+  // split tiles: not built into the COUNT(*) late-column shape (tag queries have one bucket; no room at 5 waves)
+  static constexpr bool SPLIT = !(COUNT && NL >= 1);
+  // row-major dense blocks: not in the slot-ring COUNT(*) shape (nothing to coalesce; its registers would spill)
+  static constexpr bool DENSE_BLK = NL == 0 && !(COUNT && !EARLY);
+  // COUNT(*) rows whose bucket needs no timestamp: counted with no per-row load
+  static constexpr bool COUNT_NOLOAD = COUNT && NL == 0;
+  static_assert(ROT || PF <= 2, "ring slots: rounds unrolled up to 2");
+};
 
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 
@@ -206,12 +174,13 @@ __device__ __forceinline__ void lean_rep(uint32_t v, uint32_t& w0, uint32_t& w1,
 }
 
 // EARLY (NL > 0, a late filter leaf: P.late_chunk): tiles that allow it decode the late columns per chunk (early_late
-// below); its own kernel, built for 4 waves per SIMD, so the other shapes keep their occupancy.
+// below); its own kernel, so the other shapes keep their occupancy.  NL = 0 with EARLY (P.late_chunk set by the host
+// when the filter passes a quarter or more of the name values: the dense query): the per-lane loop and row-major dense
+// blocks, the shape those tiles measured best in.  Every per-instantiation choice is in LeanShape.
 template <int AGG, bool HASH, int NL, bool EARLY = false>
-// NL = 0 with EARLY (P.late_chunk set by the host when the filter passes a quarter or more of the name values: the
-// dense query): the per-lane loop and row-major dense blocks at 5 waves per SIMD, the shape those tiles measured best in
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (NL == 0 ? LK_LEAN_WAVES1 : 4) : LEAN_WAVES(NL, AGG)))) void scan_lean(QParams P) {
-  using LT = LeanLds<NL, (NL > 0 || (LK_LEAN_LIST0 && AGG != AGG_COUNT && !EARLY))>;
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LeanShape<AGG, NL, EARLY>::WAVES))) void scan_lean(QParams P) {
+  using SH = LeanShape<AGG, NL, EARLY>;
+  using LT = LeanLds<NL, SH::LISTED>;
   __shared__ LT L;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -239,9 +208,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
   int64_t tbl = 0;
   uint32_t tspan = 0;   // buckets of the direct table (0: hash table)
   if (!HASH && P.dir_span) {
-    auto bucket_of = [&](int64_t ts) __attribute__((always_inline)) -> int64_t {   // monotone in ts
-      if (P.metrics) return (ts - P.bucket_base) / P.step;
-      return ((ts - ts % P.step) - P.bucket_base) / P.step;
+    auto bucket_of = [&](int64_t ts) __attribute__((always_inline)) -> int64_t {
+      return bucket_mono(ts, P.step, P.bucket_base, P.metrics != 0);
     };
     const int64_t lo_ts = tdp->ts_min > win_lo ? tdp->ts_min : win_lo;
     const int64_t hi_ts = tdp->ts_max < win_hi - 1 ? tdp->ts_max : win_hi - 1;
@@ -458,10 +426,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
     const int64_t tmin = tdp->ts_min, tmax = tdp->ts_max;
     if (tmin >= win_lo && tmax < win_hi) {
       if (P.metrics) {
-        if (tmin == tmax && (tmin - P.bucket_base) % P.step == 0) tile_b = (tmin - P.bucket_base) / P.step;
+        if (tmin == tmax && (tmin - P.bucket_base) % P.step == 0) tile_b = bucket_mono(tmin, P.step, P.bucket_base, true);
       } else {
-        const int64_t b0 = ((tmin - tmin % P.step) - P.bucket_base) / P.step;
-        const int64_t b1 = ((tmax - tmax % P.step) - P.bucket_base) / P.step;
+        const int64_t b0 = bucket_mono(tmin, P.step, P.bucket_base, false);
+        const int64_t b1 = bucket_mono(tmax, P.step, P.bucket_base, false);
         if (b0 == b1) tile_b = b0;
       }
       if (tile_b >= int64_t(P.nbuckets)) tile_b = -1;
@@ -479,11 +447,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
   uint32_t sb[LEAN_SPLIT_MAX];
 #pragma unroll
   for (uint32_t k = 0; k < LEAN_SPLIT_MAX; k++) sb[k] = 0u;
-  // (not built into the COUNT(*) late-column shape: tag queries have one bucket, and its 5-wave budget has no room)
-  constexpr bool SPLIT = !(AGG == AGG_COUNT && NL >= 1);
-  if (SPLIT && !one_bucket && !P.metrics && (tdp->pad & TILE_TS_SORTED) && P.split_ok) {
+  if (SH::SPLIT && !one_bucket && !P.metrics && (tdp->pad & TILE_TS_SORTED) && P.split_ok) {
     auto bucket_of = [&](int64_t ts) __attribute__((always_inline)) -> int64_t {
-      return ((ts - ts % P.step) - P.bucket_base) / P.step;
+      return bucket_mono(ts, P.step, P.bucket_base, false);
     };
     const int64_t lo_ts = tdp->ts_min > win_lo ? tdp->ts_min : win_lo;
     const int64_t hi_ts = tdp->ts_max < win_hi - 1 ? tdp->ts_max : win_hi - 1;
@@ -499,7 +465,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
     auto cls_of = [&](int64_t ts) __attribute__((always_inline)) -> uint32_t {
       if (ts < win_lo) return 0u;
       if (ts >= win_hi) return nsb;
-      return uint32_t(((ts - ts % P.step) - P.bucket_base) / P.step - split_bl) + 1u;
+      return uint32_t(bucket_mono(ts, P.step, P.bucket_base, false) - split_bl) + 1u;
     };
     auto sample = [&](uint32_t t) __attribute__((always_inline)) -> uint32_t {   // row of sample t (t = 256: nrows)
       return uint32_t((uint64_t(t) * nrows) >> 8);
@@ -567,14 +533,33 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
     for (int k = 0; k < NL; k++)
       if ((lpres >> k) & 1u) early_late = early_late && ((llut_on >> k) & 1u) && lbw[k] <= 7u;
   }
-  // early_late COUNT(*) tiles inside one bucket of the direct table (tag queries): rows counted in the chunk loop
-  const bool direct_count = early_late && AGG == AGG_COUNT && P.rows_only && one_bucket && tspan && !P.nvl &&
-                            uint64_t(tile_b - tbl) < uint64_t(tspan);
 
   Acc acc;
   acc_reset<AGG>(acc, EMPTY);
-  // a register cell into the tile's table: its direct cell (LDS atomics), HBM (a bucket beyond the direct table's
-  // span), or the LDS hash table
+  // `rows` rows -- their sum hi + lo, their ordered extreme ext -- into direct-table cell x (LDS atomics)
+  auto dir_add = [&](uint32_t x, uint32_t rows, double hi, double lo, unsigned long long ext) __attribute__((always_inline)) {
+    if (AGG == AGG_SUM) {
+      const double h = hi + 0.0;   // never -0.0 (the empty marker)
+      if (P.exact_sum) {   // exact adds: nothing to compensate
+        __hip_atomic_fetch_add(reinterpret_cast<double*>(rv + x), h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      } else {
+        const double old = atomicAdd(reinterpret_cast<double*>(rv + x), h);
+        double s, e;
+        two_sum(old, h, s, e);
+        const double c = lo + e;
+        if (c != 0.0) atomicAdd(reinterpret_cast<double*>(rlo + x), c);
+      }
+    } else if (AGG == AGG_MIN) {
+      atomicMin(rv + x, ext);
+    } else if (AGG == AGG_MAX) {
+      atomicMax(rv + x, ext);
+    } else {
+      atomicAdd(rv + x, (unsigned long long)rows);
+    }
+    if (rrows_on) atomicAdd(rrows + x, (unsigned long long)rows);
+  };
+  // a register cell into the tile's table: its direct cell, HBM (a bucket beyond the direct table's span), or the LDS
+  // hash table
   auto flush = [&]() __attribute__((always_inline)) {
     if (acc.rows == 0) return;
     if (!tspan && P.global_cells) {   // (uniform) a group space far beyond the LDS table: straight to HBM
@@ -584,29 +569,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
     } else if (acc.key & GBIT) {
       global_merge<AGG, HASH>(P, acc.key & ~GBIT, acc.rows, acc.cnt, acc.hi, acc.lo, acc.ext);
     } else {
-      const uint32_t x = uint32_t(acc.key);
-      if (AGG == AGG_SUM) {
-        const double h = acc.hi + 0.0;   // never -0.0 (the empty marker)
-        if (P.exact_sum) {   // exact adds: nothing to compensate
-          __hip_atomic_fetch_add(reinterpret_cast<double*>(rv + x), h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        } else {
-          const double old = atomicAdd(reinterpret_cast<double*>(rv + x), h);
-          double s, e;
-          two_sum(old, h, s, e);
-          const double c = acc.lo + e;
-          if (c != 0.0) atomicAdd(reinterpret_cast<double*>(rlo + x), c);
-        }
-      } else if (AGG == AGG_MIN) {
-        atomicMin(rv + x, acc.ext);
-      } else if (AGG == AGG_MAX) {
-        atomicMax(rv + x, acc.ext);
-      } else {
-        atomicAdd(rv + x, (unsigned long long)acc.rows);
-      }
-      if (rrows_on) atomicAdd(rrows + x, (unsigned long long)acc.rows);
+      dir_add(uint32_t(acc.key), acc.rows, acc.hi, acc.lo, acc.ext);
     }
   };
-  // one passing row: bucket (BaseExpr.scala:159-165 window, 163-165 / 376-394 bucket), cell, register cell
+  // one passing row: bucket (the rule of bucket.hpp's bucket_row), cell, register cell
   auto row = [&](int64_t ts, double v, uint32_t dim, uint32_t r) __attribute__((always_inline)) {
     if (P.nvl) {   // numeric leaves on the value column (uniform)
       uint32_t bits = 0;
@@ -629,6 +595,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
       if (c == 0u || c >= nsb) return;   // outside the window
       b = split_bl + int64_t(c) - 1;
     } else if (!one_bucket) {
+      // bucket_row (bucket.hpp) written out: through the function this kernel's register allocation changed
       ok = ts >= win_lo && ts < win_hi;
       if (P.fast_div) {
         const uint32_t d = uint32_t(ts - P.bucket_base);
@@ -650,7 +617,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
             ok = false;
           }
         } else {
-          b = ((ts - ts % P.step) - P.bucket_base) / P.step;
+          b = bucket_mono(ts, P.step, P.bucket_base, false);
         }
       }
       if (!ok) return;
@@ -709,12 +676,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
   auto rowsN = [&](auto ncst, auto ldc, const uint32_t* rr, const bool* aa, uint32_t* dd, auto& lw, auto& lm) __attribute__((always_inline)) {
     constexpr int N = decltype(ncst)::value;
     constexpr bool LATE_DONE = decltype(ldc)::value;   // late columns decoded already (dd complete): values only
-    bool p[N], ld[N];   // ld: rows whose timestamp / value loads were issued (plan bytes)
+    bool p[N];   // rows that pass: their timestamp / value loads are issued
     v2u tt[N], xx[N];
 #pragma unroll
     for (int u = 0; u < N; u++) {
       p[u] = aa[u];
-      ld[u] = aa[u];
       tt[u] = xx[u] = v2u{0u, 0u};
     }
     auto gather = [&]() __attribute__((always_inline)) {   // timestamps / values of the passing rows
@@ -725,12 +691,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
       }
     };
     if constexpr (NL > 0 && !LATE_DONE) {
-      // with no late filter leaf every row passes, so the timestamp / value loads go out with the late-column words
-      // speculative gather (P.spec_gather): with a late filter, every listed row's timestamp / value loads go out now,
-      // with its late-column loads, instead of after the late filter -- one dependent memory round trip less per trip
-      // for the loads of the rows the filter then drops
-      const bool spec = !late_trivial && P.spec_gather;
-      if (late_trivial || spec) gather();
+      // with no late filter leaf every row passes, so the timestamp / value loads go out with the late-column words;
+      // with one, after it (gathering before the filter decides measured slower: DESIGN §3)
+      if (late_trivial) gather();
       uint32_t T[N], F[N];
 #pragma unroll
       for (int u = 0; u < N; u++) T[u] = F[u] = 0u;
@@ -771,9 +734,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
         for (int u = 0; u < N; u++) {
           const uint32_t ix = (T[u] & ~lf) | ((F[u] | lf) << P.nleaves);
           p[u] = aa[u] && ((L.ltruth[ix >> 5] >> (ix & 31)) & 1u);
-          if (!spec) ld[u] = p[u];
         }
-        if (!spec) gather();
+        gather();
       }
     } else {
       gather();
@@ -785,7 +747,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
       };
 #pragma unroll
       for (int u = 0; u < N; u++) {
-        if (!ld[u]) continue;
+        if (!p[u]) continue;
         if (ts_gather) mark(L.lines_t, (vb0 + rr[u]) * 8u, line_t0);
         if (AGG != AGG_COUNT || P.nvl) mark(L.lines_v, (vb1 + rr[u]) * 8u, line_v0);
       }
@@ -803,28 +765,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
   // until a full trip of LEAN_TRIP rows -- LEAN_ROWS per lane, every lane busy, all their late-column loads and then
   // all their value loads in flight together -- is ready, across the tile's rounds; the rest drains at the tile's end.
   uint32_t lhead = 0, ltail = 0;   // wave-uniform list positions (mod LEAN_LIST)
-  uint32_t* const wl = L.wlist[LT::LISTED ? (tid >> 6) : 0];
-  // Deferred trips (LK_LEAN_DEFER, the late-column shapes outside early_late): a trip's late-column words are issued
-  // and the trip is finished (decode, late filter, value gather, accumulate) only at the next trip or the tile's end,
-  // so its first memory round trip overlaps the chunk rounds in between instead of being waited for on the spot.
-  // Needs the unrotated chunk ring (a rotated ring's latch waits for every load in flight, the trip's included).
-  uint32_t prr[LEAN_ROWS], pdd[LEAN_ROWS];
-  bool paa[LEAN_ROWS];
-  v2u plw[LEAN_ROWS][LT::NLA];
-  uint32_t plm[LEAN_ROWS][LT::NLA];
-  bool pend = false;   // (uniform) a deferred trip is in flight
+  uint32_t* const wl = L.wlist[SH::LISTED ? (tid >> 6) : 0];
   auto list_trip = [&](auto ec, uint32_t n) __attribute__((always_inline)) {   // the n (<= LEAN_TRIP) rows at lhead
     constexpr bool ELIST = decltype(ec)::value;   // entries carry complete group terms (early_late)
-    constexpr bool DEFER = LEAN_DEFER(NL, AGG) && !ELIST;
     if (P.ablate & 0x20000u) {   // diagnostics only: listed rows dropped unprocessed (the trips' cost)
       lhead += n;
       return;
     }
     uint32_t rr[LEAN_ROWS], dd[LEAN_ROWS];
     bool aa[LEAN_ROWS];
-    if constexpr (DEFER) {
-      if (pend) rowsN(std::integral_constant<int, LEAN_ROWS>{}, ec, prr, paa, pdd, plw, plm);   // the previous trip
-    }
 #pragma unroll
     for (int u = 0; u < LEAN_ROWS; u++) {
       const uint32_t i = uint32_t(lane) + 64u * uint32_t(u);
@@ -833,21 +782,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
       rr[u] = x & 0xffffu;
       dd[u] = ELIST ? (x >> 16) : (npass > 1 ? (L.lut[x >> 16] & DIM_MASK) * stride : dim_u);
     }
-    if constexpr (DEFER) {
-      late_issue(std::integral_constant<int, LEAN_ROWS>{}, rr, aa, plw, plm);
-#pragma unroll
-      for (int u = 0; u < LEAN_ROWS; u++) {
-        prr[u] = rr[u];
-        paa[u] = aa[u];
-        pdd[u] = dd[u];
-      }
-      pend = true;
-    } else {
-      v2u lw[LEAN_ROWS][LT::NLA];
-      uint32_t lm[LEAN_ROWS][LT::NLA];
-      if constexpr (NL > 0 && !ELIST) late_issue(std::integral_constant<int, LEAN_ROWS>{}, rr, aa, lw, lm);
-      rowsN(std::integral_constant<int, LEAN_ROWS>{}, ec, rr, aa, dd, lw, lm);
-    }
+    v2u lw[LEAN_ROWS][LT::NLA];
+    uint32_t lm[LEAN_ROWS][LT::NLA];
+    if constexpr (NL > 0 && !ELIST) late_issue(std::integral_constant<int, LEAN_ROWS>{}, rr, aa, lw, lm);
+    rowsN(std::integral_constant<int, LEAN_ROWS>{}, ec, rr, aa, dd, lw, lm);
     lhead += n;
   };
   auto wave_sync = [&]() __attribute__((always_inline)) {   // the wave's list writes / reads are ordered
@@ -876,9 +814,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
     // The packed codes of the next PF rounds are in flight while a round runs (a register ring; loads return in issue
     // order, so a round waits only for its own chunk): a round's own work is far shorter than a memory round trip, and
     // one load per lane in flight would leave the tile's stream latency-bound (PF = 0: loaded in the round itself).
-    constexpr int PF = NL == 0 ? (EARLY ? LK_LEAN_PF0E : AGG == AGG_COUNT ? LK_LEAN_PF0C : LK_LEAN_PF0)
-                               : (NL == 1 ? (AGG == AGG_COUNT ? LK_LEAN_PF1 : (LEAN_DEFER(NL, AGG) ? LK_LEAN_PF1D : LK_LEAN_PF1V))
-                                          : (LEAN_DEFER(NL, AGG) ? LK_LEAN_PF2D : LK_LEAN_PF2));
+    constexpr int PF = SH::PF;
     auto chunk_load = [&](uint32_t qq) __attribute__((always_inline)) {
       const bool lv = qq < total;
       const LeanRun Rn = L.runs[lv ? L.ctab[qq] : 0u];
@@ -928,7 +864,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
       }
     };
     if constexpr (ECH) late_load(uint32_t(tid));
-    // Ring slots (LK_LEAN_SLOTS, r06): outside the early_late bodies round j consumes slot j % PF and refills it right
+    // Ring slots (r06): the NL = 0 shapes' round j consumes slot j % PF and refills it right
     // after the slot's last use, and the rounds run PF at a time (the loop below), so each slot keeps its registers.  A
     // rotated ring (x = xr[0]; xr[i] = xr[i + 1]) copies the newest load's registers at the loop latch, and that copy
     // waits for the load (s_waitcnt vmcnt(0): the counter retires in order) -- one exposed memory round trip per round
@@ -936,7 +872,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
     // load-free COUNT rows below).  The late-column shapes keep the rotated ring: their list trips wait on their own
     // loads, which drains the ring either way (tag 0.969 / 0.973 ms, C4 1.351 / 1.351), and C3's three unrolled rounds
     // spill (1.80 -> 1.86 ms); C2 measured the same both ways (1.105 ms) and keeps the slots.
-    constexpr bool ROT = PF > 0 && (ECH || (NL > 0 && !LEAN_DEFER(NL, AGG)) || !LK_LEAN_SLOTS);
+    constexpr bool ROT = SH::ROT;
     auto round = [&](uint32_t q0, auto slc) __attribute__((always_inline)) {
       constexpr int S = decltype(slc)::value;   // the ring slot this round consumes (unrotated ring)
       const uint32_t q = q0 + uint32_t(tid);
@@ -1012,8 +948,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
       // (not built into the unrotated-ring COUNT(*) shape: its rows gather nothing to coalesce unless the timestamps are
       // unsorted, and the block's registers would spill inside the round -- a spill reload waits like any load; the
       // host sends dense filters to the EARLY shape, which keeps the block)
-      constexpr bool DENSE_BLK = NL == 0 && !(AGG == AGG_COUNT && !EARLY && LK_LEAN_SLOTS);
-      if (DENSE_BLK && dense_codes) {   // uniform
+      if (SH::DENSE_BLK && dense_codes) {   // uniform
         // Dense block: the wave's 64 chunks are 1024 row-contiguous rows and most chunks pass several rows.  The
         // per-lane loop below would have each load instruction touch 64 different 128-B lines (8 B used of each,
         // the other 120 B re-fetched by later trips -- evicted from L2 in between when every row passes), so the
@@ -1081,24 +1016,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
               if (ddir) {   // uniform: straight into the direct-table cell (neighbouring rows rarely share it)
                 const uint32_t x = dbase + dd[u] * rep;
                 min_nan_check<AGG>(P, true, v);
-                if (AGG == AGG_SUM) {
-                  const double h = v + 0.0;   // never -0.0 (the empty marker)
-                  if (P.exact_sum) {
-                    __hip_atomic_fetch_add(reinterpret_cast<double*>(rv + x), h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                  } else {
-                    const double old = atomicAdd(reinterpret_cast<double*>(rv + x), h);
-                    double s, e;
-                    two_sum(old, h, s, e);
-                    if (e != 0.0) atomicAdd(reinterpret_cast<double*>(rlo + x), e);
-                  }
-                } else if (AGG == AGG_MIN) {
-                  atomicMin(rv + x, dbl_order(v));
-                } else if (AGG == AGG_MAX) {
-                  atomicMax(rv + x, dbl_order(v));
-                } else {
-                  atomicAdd(rv + x, 1ull);
-                }
-                if (rrows_on) atomicAdd(rrows + x, 1ull);
+                dir_add(x, 1u, v, -0.0, dbl_order(v));   // lo = -0.0: x + -0.0 is x for every x
               } else {
                 row((int64_t)(((uint64_t)tt[u].y << 32) | tt[u].x), v, dd[u], rb0 + 64u * uint32_t(j0 + u) + uint32_t(lane));
               }
@@ -1107,8 +1025,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
           m = 0;
         }
       }
-      constexpr bool LIST0 = NL == 0 && LK_LEAN_LIST0 && AGG != AGG_COUNT && !EARLY;
-      if (AGG == AGG_COUNT && NL == 0 && LK_LEAN_SLOTS && !ts_gather && !P.nvl) {   // uniform
+      if (SH::COUNT_NOLOAD && !ts_gather && !P.nvl) {   // uniform
         // COUNT(*) with every row's bucket from the zone map or the split: no per-row load, so no loop here carries
         // one (a wait at its head would drain the chunk ring too).  One passing code and no split boundary inside the
         // chunk: the chunk's rows are one register-cell add of their popcount.
@@ -1128,7 +1045,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
             row(0, 0.0, d, rbase + e);
           }
         }
-      } else if (!LT::LISTED || (NL == 0 && (!LIST0 || dense_codes))) {   // uniform
+      } else if (!SH::LISTED || (SH::LIST0 && dense_codes)) {   // uniform
         // passing rows: two per trip (their loads in flight together)
         while (m) {
           const uint32_t e1 = uint32_t(__builtin_ctzll(m)) >> shs;
@@ -1148,7 +1065,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
           uint32_t lm[2][LT::NLA];
           rowsN(std::integral_constant<int, 2>{}, std::false_type{}, rr, aa, dd, lw, lm);
         }
-      } else if constexpr (LT::LISTED) {
+      } else if constexpr (SH::LISTED) {
         // Late columns: the wave's passing rows are appended to its LDS list (lane-major) and processed LEAN_TRIP at
         // a time (list_trip) -- a per-lane loop would run as many trips as the lane with the most passing rows, each
         // a chain of dependent late-column and value loads.
@@ -1212,30 +1129,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
           fm = f16;
           fs = 0;
         }
-        if constexpr (ECH) {
-          // COUNT(*) into a one-bucket direct table (tag queries): the chunk's late codes are in
-          // its window already, so a passing row is counted right here -- no list, no per-row late-column load
-          if (direct_count) {   // uniform
-            const uint32_t base = uint32_t(tile_b - tbl) * ngr;
-            uint32_t f = f16;
-            while (f) {
-              const uint32_t e = uint32_t(__builtin_ctz(f));
-              f &= f - 1u;
-              const uint32_t code = lit ? lean_code<BW>(w0, w1, w2, e) : rval;
-              uint32_t term = npass > 1 ? (L.lut[code] & DIM_MASK) * stride : dim_u;
-#pragma unroll
-              for (int k = 0; k < NL; k++) {
-                const StrParam& sp = P.strp[1 + k];
-                term += ((lpres >> k) & 1u) ? (L.llut[k][late_code(k, e)] & DIM_MASK) * sp.dim_stride
-                                            : sp.dim_null * sp.dim_stride;
-              }
-              const uint32_t x = (base + term) * rep + myrep;
-              atomicAdd(rv + x, 1ull);
-              if (rrows_on) atomicAdd(rrows + x, 1ull);
-            }
-            return;   // (uniform) the next round of chunks
-          }
-        }
         if (P.ablate & 0x10000u) fm = 0;   // diagnostics only: no row listed (the chunk filter's cost alone)
         const uint32_t cnt = uint32_t(__popcll(fm));
         uint32_t inc = cnt;
@@ -1280,21 +1173,13 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EARLY ? (
     if constexpr (ROT || PF <= 1) {
       for (uint32_t q0 = 0; q0 < total; q0 += BLOCK) round(q0, std::integral_constant<int, 0>{});   // uniform trip count
     } else {
-      for (uint32_t q0 = 0; q0 < total; q0 += uint32_t(PF) * BLOCK) {   // uniform: PF rounds, slots 0 .. PF - 1
+      for (uint32_t q0 = 0; q0 < total; q0 += uint32_t(PF) * BLOCK) {   // uniform: PF = 2 rounds, slots 0 and 1
         round(q0, std::integral_constant<int, 0>{});
         if (q0 + BLOCK < total) round(q0 + BLOCK, std::integral_constant<int, 1>{});
-        if constexpr (PF > 2) {
-          if (q0 + 2u * BLOCK < total) round(q0 + 2u * BLOCK, std::integral_constant<int, 2>{});
-        }
-        static_assert(PF <= 3, "ring slots: rounds unrolled up to 3");
       }
     }
-    if constexpr (LT::LISTED) {
+    if constexpr (SH::LISTED) {
       while (ltail != lhead) list_trip(ec, min(LEAN_TRIP, ltail - lhead));   // the tile's last rows
-      if constexpr (LEAN_DEFER(NL, AGG) && !ECH) {
-        if (pend) rowsN(std::integral_constant<int, LEAN_ROWS>{}, ec, prr, paa, pdd, plw, plm);   // the last trip
-        pend = false;
-      }
       wave_sync();
     }
   };

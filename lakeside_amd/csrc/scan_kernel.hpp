@@ -22,6 +22,7 @@
 #pragma once
 #include <type_traits>
 
+#include "bucket.hpp"
 #include "device_common.hpp"
 
 namespace lk {
@@ -304,10 +305,6 @@ __device__ __forceinline__ uint32_t g8_bits(const G8& g, __amdgpu_buffer_rsrc_t 
   return bits;
 }
 
-#ifndef LK_DEPTH   // software-pipeline depth per string-column count (ring of pending chunks, see the main loop)
-#define LK_DEPTH(nstr) 1
-#endif
-
 // Listed rows of a wave whose timestamp/value loads are in flight: NS slots of 64 rows (one row per lane per slot).
 template <int NS>
 struct ChunkT {
@@ -554,10 +551,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NSTR == 1
     const int64_t tmin = tdp->ts_min, tmax = tdp->ts_max;
     if (tmin >= win_lo && tmax < win_hi) {
       if (P.metrics) {
-        if (tmin == tmax && (tmin - P.bucket_base) % P.step == 0) tile_b = (tmin - P.bucket_base) / P.step;
+        if (tmin == tmax && (tmin - P.bucket_base) % P.step == 0) tile_b = bucket_mono(tmin, P.step, P.bucket_base, true);
       } else {
-        const int64_t b0 = ((tmin - tmin % P.step) - P.bucket_base) / P.step;
-        const int64_t b1 = ((tmax - tmax % P.step) - P.bucket_base) / P.step;
+        const int64_t b0 = bucket_mono(tmin, P.step, P.bucket_base, false);
+        const int64_t b1 = bucket_mono(tmax, P.step, P.bucket_base, false);
         if (b0 == b1) tile_b = b0;
       }
       if (tile_b >= int64_t(P.nbuckets)) tile_b = -1;   // out of the cell space: the per-row path flags it
@@ -644,10 +641,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NSTR == 1
       const int64_t ts = (int64_t)(((uint64_t)ch.ts[j].y << 32) | ch.ts[j].x);
       bool ok = ((ch.live >> j) & 1u) && (one_bucket || (ts >= win_lo && ts < win_hi));   // BaseExpr.scala:159-161
       int64_t b = 0;
+      // bucket_row (bucket.hpp) written out: through the function this kernel's register allocation changed
       if (one_bucket) {
         b = tile_b;
       } else if (P.fast_div) {
-        // d < 2^32: q from the double reciprocal is off by at most one; fix with the remainder
         const uint32_t d = uint32_t(ts - P.bucket_base);
         uint32_t q = uint32_t(double(d) * P.inv_step);
         int64_t rm = int64_t(d) - int64_t(q) * step32;
@@ -667,7 +664,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NSTR == 1
             ok = false;
           }
         } else {
-          b = ((ts - ts % P.step) - P.bucket_base) / P.step;        // ts - ts % step (fmod, truncation)
+          b = bucket_mono(ts, P.step, P.bucket_base, false);
         }
       }
       if (!ok) continue;
@@ -692,11 +689,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NSTR == 1
       acc_add<AGG>(acc, vvalid, v);
     }
   };
-  // Software pipeline: the first 64 listed rows of sub-tile k are issued into ring slot k % DEPTH and consumed
-  // DEPTH sub-tiles later, after that many decodes have overlapped their timestamp/value (or late-column) loads:
-  // the loop is unrolled DEPTH times so every ring slot keeps its own registers (moving a register a load is still
-  // writing would wait for the load).  Further listed rows of a sub-tile (dense filters) stream at once.
-  constexpr int DEPTH = LK_DEPTH(NSTR);
+  // Software pipeline: the first 64 listed rows of a sub-tile are issued into `pend` and consumed one sub-tile
+  // later, after that sub-tile's decode has overlapped their timestamp/value (or late-column) loads.  Further listed
+  // rows of a sub-tile (dense filters) stream at once.
   const bool stream_on = !(P.ablate & 1);
 
   // Late stage (late_ok tiles), one row per lane: the listed row's late columns' packed words in flight.
@@ -1032,8 +1027,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NSTR == 1
         }
       }
     }
-    // The ring slot's chunk (issued DEPTH sub-tiles ago) has had DEPTH decodes to land; this sub-tile's first
-    // 64 listed rows take its place.  Further chunks (dense filters) stream at once.
+    // The pending chunk (issued one sub-tile ago) has had a decode to land; this sub-tile's first 64 listed rows
+    // take its place.  Further chunks (dense filters) stream at once.
     if (stream_on && !late_done) {
       consume(ring);
       ring.n = 0;
@@ -1051,23 +1046,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NSTR == 1
     __builtin_amdgcn_wave_barrier();
     LK_STAMP(7)
   };
-  ChunkT<1> q0, q1, q2;
-  q0.n = q1.n = q2.n = 0;
-  for (uint32_t sub = 0; sub < tile_nrows; sub += DEPTH * SUBT) {
-    step(q0, sub);
-    if constexpr (DEPTH > 1) {
-      if (sub + SUBT < tile_nrows) step(q1, sub + SUBT);
-    }
-    if constexpr (DEPTH > 2) {
-      if (sub + 2 * SUBT < tile_nrows) step(q2, sub + 2 * SUBT);
-    }
-  }
-  // drain: the ring's chunks still in flight, then the last late chunk's survivors
-  if (stream_on) {
-    consume(q0);
-    if constexpr (DEPTH > 1) consume(q1);
-    if constexpr (DEPTH > 2) consume(q2);
-  }
+  ChunkT<1> pend;
+  pend.n = 0;
+  for (uint32_t sub = 0; sub < tile_nrows; sub += SUBT) step(pend, sub);
+  // drain: the chunk still in flight, then the last late chunk's survivors
+  if (stream_on) consume(pend);
   if constexpr (NSTR > 1) {
     if (lpend.n) {
       uint32_t g;
