@@ -50,6 +50,17 @@ int lk_ex_select_sim(const int64_t* ts, size_t n, int64_t win_lo, int64_t win_hi
 void lk_bucket_sim(const int64_t* ts, size_t n, int64_t win_lo, int64_t win_hi, int64_t step, int64_t base,
                    uint64_t nbuckets, int metrics, int fast_div, int64_t* bucket, uint8_t* status, int64_t* mono);
 
+/* Plans the filter of a PushDownRequest as the evaluator does before it reads a segment (lakeside_amd/csrc/
+ * filter_plan.cpp: the leaf loop of the shape gate, plan_filter, plan_truth); numeric_group_bys[0..n) are the groupBys
+ * to take as columns stored as numbers (the evaluator learns them from the loaded files).  Writes a JSON object into out
+ * (NUL-terminated): cols (the string columns' names), leaves ({col: string column or -1, op, index, k}), nums (the
+ * numeric query columns), nleaves ({col, leaf, lo_incl, hi_incl, nan_pass}), prog (the postfix program's bytes), truth /
+ * truth_x / truth_early / truth_late (32-bit words as hex text; bit T | F << L of a table = TRUE), vtab, vleaf,
+ * vleaf_shape, early, late_mask, dev_of, lead.  Returns 0; a PlanError's code (LK_ERR_ARG -1, LK_ERR_UNSUPPORTED -2)
+ * with its message in out; -5 when cap is too small for the plan.  Reads LK_NO_VLEAF / LK_NO_EARLY_FIRST as the
+ * evaluator does. */
+int lk_filter_plan_sim(const char* request_json, const char* const* numeric_group_bys, size_t n, char* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

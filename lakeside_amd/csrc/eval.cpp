@@ -1234,6 +1234,15 @@ void write_stats(const EvalCall& C, const Plan& pl, const DevState& dv, const Co
     snprintf(b3, sizeof(b3), "],\"numdim_ms\":%.6f,\"numdim_attempts\":%d", pl.dp.nd.ms, pl.dp.nd.attempts);
     C.res->stats += nd + b3;
   }
+  {   // which filter path ran: table (<= TT_MAX_LEAVES leaves) or interpreter, the early / late split, the lean kernels
+    char b4[192];
+    snprintf(b4, sizeof(b4),
+             ",\"filter\":{\"leaves\":%zu,\"table\":%d,\"early\":%d,\"late_mask\":%u,\"vleaf\":%d},\"lean_split\":%u,"
+             "\"late_chunk\":%u",
+             pl.fp.leaves.size(), pl.fp.truth.empty() ? 0 : 1, pl.fp.early, pl.fp.late_mask, pl.fp.vleaf ? 1 : 0,
+             dv.P.lean_split, dv.P.late_chunk);
+    C.res->stats += b4;
+  }
   C.res->stats += "}";
 }
 }  // namespace

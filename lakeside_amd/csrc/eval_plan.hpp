@@ -259,6 +259,12 @@ void plan_segments(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp
                    SegPlan& sg);
 void plan_table_mode(const QueryShape& qs, const SegPlan& sg, CellSpace& cs);
 
+// The pure part of the filter planning (filter_plan.cpp: the request and the shape alone, no Engine, no HIP call):
+// shape_gate's leaf loop (all_leaves, nums, numeric), and what plan_filter / plan_truth do for a call.
+void shape_leaves(const Request& R, QueryShape& qs);
+void plan_filter(const Request& R, const QueryShape& qs, FilterPlan& fp);
+void plan_truth(const Request& R, const QueryShape& qs, FilterPlan& fp);
+
 // The result's tag columns (eval_rows.cpp).
 void label_rows(const EvalCall& C, const Plan& pl, uint32_t nrows_out);
 

@@ -1,5 +1,5 @@
 // Plan helpers shared by the aggregate evaluator (eval_plan.cpp, eval.cpp) and the exemplar path (exemplar.cpp);
-// defined in eval_plan.cpp unless noted.
+// defined in eval_plan.cpp unless noted (the filter tree's: filter_plan.cpp).
 #pragma once
 #include <algorithm>
 #include <chrono>
