@@ -61,6 +61,24 @@ void lk_bucket_sim(const int64_t* ts, size_t n, int64_t win_lo, int64_t win_hi, 
  * evaluator does. */
 int lk_filter_plan_sim(const char* request_json, const char* const* numeric_group_bys, size_t n, char* out, size_t cap);
 
+/* Numeric groupBys, the two rules the ranks of a distributed evaluation apply to agreed data (lakeside_amd/csrc/
+ * numgroup_agree.cpp; the evaluator calls the same functions, sharded or not).
+ * Classes.  A (groupBy column, glob) travels as 3 bytes per rank: a VARCHAR file, a BOOLEAN file, the largest value rank
+ * of a numeric file (INT32 1 < INT64 2 < FLOAT 3 < DOUBLE 4; 0 none).  lk_numgroup_file_class writes the bytes of one
+ * file's column (Parquet physical type; is_string: a VARCHAR column); a rank's bytes are the element-wise max over its
+ * files.  lk_numgroup_classes_sim takes n_ranks x 3 bytes and returns 0 with *union_type = the glob's union_by_name type
+ * as a Parquet physical type (BOOLEAN 0, INT32 1, INT64 2, FLOAT 4, DOUBLE 5, BYTE_ARRAY 6 for VARCHAR alone, -1 when no
+ * file has the column), or the refused union: 1 VARCHAR with BOOLEAN / numeric files, 2 BOOLEAN with numeric files
+ * (*union_type = -1); -1 (LK_ERR_ARG) for a rank byte above 4.
+ * Values.  Per rank r, counts[r] entries (union type, canonical key: ex_kernels.hip tag_key) of one column, concatenated
+ * in rank order.  Writes the sorted distinct JDBC getString texts, '\n'-separated and NUL-terminated, into out, and the
+ * position of every entry's text into ids; returns the number of texts, -5 when cap is too small, or a PlanError's code
+ * with its message in out. */
+int lk_numgroup_file_class(int is_string, int ptype, uint8_t* out3);
+int lk_numgroup_classes_sim(const uint8_t* classes, size_t n_ranks, int* union_type);
+long lk_numgroup_values_sim(const int32_t* union_types, const uint64_t* keys, const size_t* counts, size_t n_ranks,
+                            uint32_t* ids, char* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

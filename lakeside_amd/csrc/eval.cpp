@@ -504,6 +504,9 @@ XParams general_scan_params(const Plan& pl, const DevState& dv, uint32_t mode) {
 // canonical keys of every numeric group column per glob (tables regrown x8 while one overflows, as TAGNUM's); the host
 // prints each (glob union type, key) as JDBC getString does, orders the distinct texts of all globs -- a dimension's
 // ids depend on the set of texts alone -- and uploads the id of every slot for the aggregate scan's lookup.
+// Distributed: every rank discovers over its own segments, one all-gather carries every rank's text sets with its
+// status, and the sorted union over the ranks is the dimension on every rank (ids never depend on a rank, a slot or
+// timing).  The rank-local steps run inside comm_local: a failure travels with the next agreement, no rank unwinds alone.
 void discover_numdims(const EvalCall& C, Plan& pl, const DevState& dv) {
   const auto t0 = std::chrono::steady_clock::now();
   NumDimTables& nd = pl.dp.nd;
@@ -514,74 +517,106 @@ void discover_numdims(const EvalCall& C, Plan& pl, const DevState& dv) {
     while (p < x) p <<= 1;
     return p;
   };
-  std::vector<uint64_t> grows(ng, 0);
-  for (size_t gi = 0; gi < ng; gi++)
-    for (int si : pl.gp.globs[gi].segs)
-      if (pl.gp.segs[si]) grows[gi] += uint64_t(pl.gp.segs[si]->num_rows);
-  const uint64_t cap_max = std::max<uint64_t>(1 << 12, pow2(2 * *std::max_element(grows.begin(), grows.end())));
-  uint64_t cap = std::min<uint64_t>(cap_max, pow2(env_u64("LK_NUMDIM_INIT_SLOTS", uint64_t(1) << 12, 64)));
   std::vector<unsigned long long> keys;
   std::vector<uint32_t> ones(ng * nnd, 0);
+  std::vector<std::vector<std::string>> mine(nnd);   // per column: this process's distinct texts, sorted
   hipStream_t st = dv.st;
-  if (nseg && pl.cs.ncells && (!dv.hbuf || !dv.dbuf)) throw PlanError(LK_ERR_DEVICE, "internal: numeric groupBy without a staged query");
-  for (;;) {
-    nd.attempts++;
-    const size_t nslots = ng * nnd * size_t(cap);
-    // [keys | ids | all-ones words | flags | segment -> glob]
-    const size_t o_ids = nslots * 8, o_ones = o_ids + nslots * 4, o_flags = o_ones + ng * nnd * 4, o_sg = o_flags + 16;
-    uint8_t* tb = static_cast<uint8_t*>(C.X.workspace("numdim", o_sg + nseg * 4 + 64));
-    nd.cap = cap;
-    nd.d_keys = reinterpret_cast<unsigned long long*>(tb);
-    nd.d_ids = reinterpret_cast<uint32_t*>(tb + o_ids);
-    nd.d_ones = reinterpret_cast<uint32_t*>(tb + o_ones);
-    nd.d_flags = reinterpret_cast<uint32_t*>(tb + o_flags);
-    nd.d_seg_glob = reinterpret_cast<const uint32_t*>(tb + o_sg);
-    HIP_TRY(hipMemsetAsync(tb, 0xff, nslots * 8, st));
-    HIP_TRY(hipMemsetAsync(tb + o_ids, 0, o_sg - o_ids, st));
-    if (nseg) HIP_TRY(hipMemcpyAsync(tb + o_sg, pl.sg.gseg_glob.data(), nseg * 4, hipMemcpyHostToDevice, st));
-    if (pl.cs.ncells && nseg) HIP_TRY(launch_ex_scan_numdim(general_scan_params(pl, dv, XMODE_NUMDIM), st));
-    uint32_t fl = 0;
-    HIP_TRY(hipMemcpyAsync(&fl, nd.d_flags, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (!(fl & FLAG_HASH_FULL)) break;
-    if (cap >= cap_max) throw PlanError(LK_ERR_MEMORY, "numeric groupBy: value table full at its bound");
-    cap = std::min(cap_max, cap * 8);
-  }
-  const size_t nslots = ng * nnd * size_t(nd.cap);
-  keys.resize(nslots);
-  HIP_TRY(hipMemcpyAsync(keys.data(), nd.d_keys, nslots * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(ones.data(), nd.d_ones, ones.size() * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  std::vector<uint32_t> ids(nslots, 0);
-  for (size_t k = 0; k < nnd; k++) {
-    DimCol& dc = pl.dp.dims[first + k];
-    auto text_of = [&](size_t gi, unsigned long long key) {
-      const int ut = pl.gp.num_ut[k][gi];
-      if (ut < 0) throw PlanError(LK_ERR_DEVICE, "internal: numeric groupBy value in a glob without the column");
-      return value_text(key, ut, ut);
-    };
-    std::set<std::string> texts;
-    for (size_t gi = 0; gi < ng; gi++) {
-      const unsigned long long* tk = keys.data() + (gi * nnd + k) * size_t(nd.cap);
-      for (size_t s2 = 0; s2 < nd.cap; s2++)
-        if (tk[s2] != TAG_EMPTY) texts.insert(text_of(gi, tk[s2]));
-      if (ones[gi * nnd + k]) texts.insert(text_of(gi, TAG_EMPTY));
+  auto text_of = [&](size_t k, size_t gi, unsigned long long key) { return numdim_key_text(pl.gp.num_ut[k][gi], key); };
+  // run a rank-local step: alone it throws; distributed, its failure is kept for the next agreement
+  auto local = [&](auto&& f) {
+    if (C.dist) comm_local(C.X, f);
+    else f();
+  };
+  local([&] {
+    if (C.dist) fault_point(C.E, "numdim");
+    if (dv.local_err) throw PlanError(dv.local_err, dv.local_msg);   // (distributed: the staging failed on this rank)
+    std::vector<uint64_t> grows(ng, 0);
+    for (size_t gi = 0; gi < ng; gi++)
+      for (int si : pl.gp.globs[gi].segs)
+        if (pl.gp.segs[si]) grows[gi] += uint64_t(pl.gp.segs[si]->num_rows);
+    const uint64_t cap_max = std::max<uint64_t>(1 << 12, pow2(2 * *std::max_element(grows.begin(), grows.end())));
+    uint64_t cap = std::min<uint64_t>(cap_max, pow2(env_u64("LK_NUMDIM_INIT_SLOTS", uint64_t(1) << 12, 64)));
+    if (nseg && pl.cs.ncells && (!dv.hbuf || !dv.dbuf)) throw PlanError(LK_ERR_DEVICE, "internal: numeric groupBy without a staged query");
+    for (;;) {
+      nd.attempts++;
+      const size_t nslots = ng * nnd * size_t(cap);
+      // [keys | ids | all-ones words | flags | segment -> glob]
+      const size_t o_ids = nslots * 8, o_ones = o_ids + nslots * 4, o_flags = o_ones + ng * nnd * 4, o_sg = o_flags + 16;
+      uint8_t* tb = static_cast<uint8_t*>(C.X.workspace("numdim", o_sg + nseg * 4 + 64));
+      nd.cap = cap;
+      nd.d_keys = reinterpret_cast<unsigned long long*>(tb);
+      nd.d_ids = reinterpret_cast<uint32_t*>(tb + o_ids);
+      nd.d_ones = reinterpret_cast<uint32_t*>(tb + o_ones);
+      nd.d_flags = reinterpret_cast<uint32_t*>(tb + o_flags);
+      nd.d_seg_glob = reinterpret_cast<const uint32_t*>(tb + o_sg);
+      HIP_TRY(hipMemsetAsync(tb, 0xff, nslots * 8, st));
+      HIP_TRY(hipMemsetAsync(tb + o_ids, 0, o_sg - o_ids, st));
+      if (nseg) HIP_TRY(hipMemcpyAsync(tb + o_sg, pl.sg.gseg_glob.data(), nseg * 4, hipMemcpyHostToDevice, st));
+      if (pl.cs.ncells && nseg) HIP_TRY(launch_ex_scan_numdim(general_scan_params(pl, dv, XMODE_NUMDIM), st));
+      uint32_t fl = 0;
+      HIP_TRY(hipMemcpyAsync(&fl, nd.d_flags, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (!(fl & FLAG_HASH_FULL)) break;
+      if (cap >= cap_max) throw PlanError(LK_ERR_MEMORY, "numeric groupBy: value table full at its bound");
+      cap = std::min(cap_max, cap * 8);
     }
-    dc.cand.assign(texts.begin(), texts.end());   // sorted: dim id = position
+    const size_t nslots = ng * nnd * size_t(nd.cap);
+    keys.resize(nslots);
+    HIP_TRY(hipMemcpyAsync(keys.data(), nd.d_keys, nslots * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ones.data(), nd.d_ones, ones.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t k = 0; k < nnd; k++) {
+      std::vector<std::string> texts;
+      for (size_t gi = 0; gi < ng; gi++) {
+        const unsigned long long* tk = keys.data() + (gi * nnd + k) * size_t(nd.cap);
+        for (size_t s2 = 0; s2 < nd.cap; s2++)
+          if (tk[s2] != TAG_EMPTY) texts.push_back(text_of(k, gi, tk[s2]));
+        if (ones[gi * nnd + k]) texts.push_back(text_of(k, gi, TAG_EMPTY));
+      }
+      mine[k] = numdim_text_union({texts});
+    }
+  });
+  // the dimensions: the sorted union of every rank's texts, dim id = position
+  std::vector<std::vector<std::vector<std::string>>> sets(nnd);   // [column][rank]
+  if (C.dist) {
+    const auto t1 = std::chrono::steady_clock::now();
+    std::string blob;
+    for (size_t k = 0; k < nnd; k++) put_texts(blob, mine[k]);
+    // (a rank whose discovery failed sends its pending status: every rank throws it here)
+    const std::vector<std::string> all = comm_allgather_status(C.E, C.X, 0, std::string(), blob);
+    for (const std::string& b : all) {
+      size_t at = 0;
+      for (size_t k = 0; k < nnd; k++) sets[k].push_back(get_texts(b, at));
+    }
+    nd.exchange_bytes = blob.size();
+    nd.exchange_ms = ms_since(t1);
+  } else {
+    for (size_t k = 0; k < nnd; k++) sets[k].push_back(std::move(mine[k]));
+  }
+  for (size_t k = 0; k < nnd; k++) {   // (the bounds are checked on the union: every rank fails alike)
+    DimCol& dc = pl.dp.dims[first + k];
+    dc.cand = numdim_text_union(sets[k]);
     if (dc.cand.size() + 1 > DIM_MASK) throw PlanError(LK_ERR_UNSUPPORTED, "group dimension too large");
     dc.ndim = uint32_t(dc.cand.size()) + 1;
     dc.dim_null = uint32_t(dc.cand.size());
-    auto id_of = [&](const std::string& t) { return uint32_t(std::lower_bound(dc.cand.begin(), dc.cand.end(), t) - dc.cand.begin()); };
-    for (size_t gi = 0; gi < ng; gi++) {
-      const size_t base = (gi * nnd + k) * size_t(nd.cap);
-      for (size_t s2 = 0; s2 < nd.cap; s2++)
-        if (keys[base + s2] != TAG_EMPTY) ids[base + s2] = id_of(text_of(gi, keys[base + s2]));
-      ones[gi * nnd + k] = ones[gi * nnd + k] ? id_of(text_of(gi, TAG_EMPTY)) : dc.dim_null;
-    }
   }
-  HIP_TRY(hipMemcpyAsync(nd.d_ids, ids.data(), nslots * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(nd.d_ones, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  local([&] {
+    if (C.dist) fault_point(C.E, "numdim_ids");
+    const size_t nslots = ng * nnd * size_t(nd.cap);
+    std::vector<uint32_t> ids(nslots, 0);
+    for (size_t k = 0; k < nnd; k++) {
+      const DimCol& dc = pl.dp.dims[first + k];
+      for (size_t gi = 0; gi < ng; gi++) {
+        const size_t base = (gi * nnd + k) * size_t(nd.cap);
+        for (size_t s2 = 0; s2 < nd.cap; s2++)
+          if (keys[base + s2] != TAG_EMPTY) ids[base + s2] = numdim_id_of(dc.cand, text_of(k, gi, keys[base + s2]));
+        ones[gi * nnd + k] = ones[gi * nnd + k] ? numdim_id_of(dc.cand, text_of(k, gi, TAG_EMPTY)) : dc.dim_null;
+      }
+    }
+    HIP_TRY(hipMemcpyAsync(nd.d_ids, ids.data(), nslots * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(nd.d_ones, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  });
   nd.ms = ms_since(t0);
 }
 
@@ -1230,9 +1265,14 @@ void write_stats(const EvalCall& C, const Plan& pl, const DevState& dv, const Co
     for (size_t k = 0; k < pl.qs.numgbs.size(); k++)
       nd += std::string(k ? "," : "") + "{\"column\":\"" + json_escape(pl.qs.numgbs[k]) + "\",\"values\":" +
             std::to_string(pl.dp.dims[pl.fp.cols.size() + k].cand.size()) + "}";
-    char b3[96];
+    char b3[160];
     snprintf(b3, sizeof(b3), "],\"numdim_ms\":%.6f,\"numdim_attempts\":%d", pl.dp.nd.ms, pl.dp.nd.attempts);
     C.res->stats += nd + b3;
+    if (C.dist) {
+      snprintf(b3, sizeof(b3), ",\"numdim_exchange_ms\":%.6f,\"numdim_exchange_bytes\":%llu", pl.dp.nd.exchange_ms,
+               (unsigned long long)pl.dp.nd.exchange_bytes);
+      C.res->stats += b3;
+    }
   }
   {   // which filter path ran: table (<= TT_MAX_LEAVES leaves) or interpreter, the early / late split, the lean kernels
     char b4[192];
@@ -1248,7 +1288,8 @@ void write_stats(const EvalCall& C, const Plan& pl, const DevState& dv, const Co
 }  // namespace
 
 // One evaluation: plan -> scan -> (RCCL merge) -> finalize -> rows.  Distributed calls issue their collectives in this
-// order: the glob agreement (plan_globs), one dim union per unrestricted dim (plan_dims), the post-scan status
+// order: the glob agreement (plan_globs; once more after the re-plan of a call with numeric groupBys), one dim union per
+// unrestricted dim (plan_dims), the numeric group dimensions' value exchange (discover_numdims), the post-scan status
 // all-gathers (scan_agreed), the reduce (reduce_tables).
 static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, const char* const* paths, size_t n_paths,
                          int glob_size, unsigned flags, const int32_t* shard, bool dist, lk_result* res, unsigned redo) {
@@ -1285,6 +1326,21 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
     stage("segments");
     plan_globs(C, pl.qs, pl.fp, pl.gp);
   }
+  // Distributed numeric groupBys: which groupBys are numeric was agreed on with the glob unions, after the filter was
+  // planned from the request alone -- every rank plans again from the shape with the agreed classes (the decision comes
+  // from agreed data, so every rank takes this branch, refuses alike and issues the second glob agreement)
+  if (dist_numeric_replan(C, pl.qs, pl.gp)) {
+    const std::vector<std::string> cands = std::move(pl.gp.gb_cands);
+    const std::vector<GbClass> agreed = std::move(pl.gp.gb_class);
+    pl.qs = QueryShape{};
+    pl.fp = FilterPlan{};
+    reset_glob_plan(pl.gp);
+    shape_gate(C, pl.qs);
+    decide_numeric_group_bys(C, pl.qs, cands, agreed);
+    plan_filter(C, pl.qs, pl.fp);
+    plan_globs(C, pl.qs, pl.fp, pl.gp);
+    stage("replan");
+  }
   // A tag query over a numeric tag column (agreed among the ranks): every rank takes the TAGNUM row scan (exemplar.cpp)
   if (pl.gp.tag_numeric) {
     pl.gp.segs.clear();
@@ -1314,6 +1370,13 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
     plan_table_mode(pl.qs, pl.sg, pl.cs);
     dv = DevState{};
     stage_upload(C, pl, dv);
+    // distributed: a rank whose ids did not reach its tables scans nothing; the scan's agreement fails every rank
+    if (C.X.pend_code && !dv.local_err) {
+      dv.local_err = C.X.pend_code;
+      dv.local_msg = C.X.pend_msg;
+      C.X.pend_code = 0;
+      C.X.pend_msg.clear();
+    }
     stage("numdims");
   }
   if (pl.gp.ftab_guard.owns_lock()) pl.gp.ftab_guard.unlock();   // the table is staged: other calls may extend it

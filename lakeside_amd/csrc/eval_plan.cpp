@@ -18,6 +18,7 @@
 #include "comm.hpp"
 #include "hostutil.hpp"
 #include "layout.hpp"
+#include "numgroup_agree.hpp"
 #include "parquet.hpp"
 #include "regex.hpp"
 
@@ -90,23 +91,6 @@ LockedLeafBits extend_leaf_bits(Engine& E, const LeafCol& sc, const GlobalDict& 
 }
 
 namespace {
-// union_by_name over a glob's files unifies a numeric column to the widest of its physical types in DuckDB's order
-// INTEGER < BIGINT < FLOAT < DOUBLE (the same rule exemplar.cpp's union_type applies to tag text).  Rank 0: not a
-// numeric type a value column can have.
-int value_rank(int ptype) {
-  switch (ptype) {
-    case pq::INT32: return 1;
-    case pq::INT64: return 2;
-    case pq::FLOAT: return 3;
-    case pq::DOUBLE: return 4;
-    default: return 0;
-  }
-}
-int value_type_of_rank(int r) {
-  static const int t[5] = {-1, pq::INT32, pq::INT64, pq::FLOAT, pq::DOUBLE};
-  return t[r < 0 || r > 4 ? 0 : r];
-}
-
 // The column's FieldTab over dictionary ids [0, n) (values below n are immutable; the caller holds ft.mu).
 void extend_field_tab(FieldTab& ft, const GlobalDict& gd, uint32_t n) {
   ft.val.reserve(n);
@@ -326,43 +310,53 @@ bool numeric_gb_candidate(const EvalCall& C, const QueryShape& qs, const std::st
                       [&](const FilterNode* l) { return l->k == gb && !numeric_op(l->op); });
 }
 bool numeric_dim_type(int ptype) { return ptype == pq::BOOLEAN || value_rank(ptype) != 0; }
+size_t glob_count(const EvalCall& C) { return (C.n_paths + size_t(C.glob_size) - 1) / size_t(C.glob_size); }
+
+// One loaded file's class of candidate groupBy `gb` into its glob's (absent, or of a type the loader does not decode
+// -- refused in plan_globs: no class).
+void add_file_class(GbClass& c, const Segment& S, const std::string& gb) {
+  const int col = S.col_index(gb);
+  if (col >= 0) gb_class_add(c, S.cols[size_t(col)].is_string, S.cols[size_t(col)].ptype);
+}
 }  // namespace
+
+std::vector<std::string> numeric_gb_candidates(const EvalCall& C, const QueryShape& qs) {
+  std::vector<std::string> out;
+  for (const std::string& gb : C.R.group_bys)
+    if (std::find(out.begin(), out.end(), gb) == out.end() && numeric_gb_candidate(C, qs, gb)) out.push_back(gb);
+  return out;
+}
 
 // Numeric group dimensions.  BaseExpr.getChartSql writes `GROUP BY step_ts, "<col>", name`
 // (BaseExpr.scala:338-346, 401-403) and DuckDB groups a BIGINT / DOUBLE / BOOLEAN column like any other, each value
 // printed by JDBC getString (Commons.scala:430-437): a groupBy-only column (or one with gt/ge/lt/le leaves) that some
 // loaded file stores as INT32 / INT64 / FLOAT / DOUBLE / BOOLEAN becomes a numeric query column whose values the row
 // scan discovers (XMODE_NUMDIM) and looks up.  The unions this engine does not restate fail the whole call.
-// (Distributed calls are refused as a whole, agreed on in plan_globs.)
-void plan_numeric_group_bys(const EvalCall& C, QueryShape& qs, const GlobPlan& gp) {
-  if (C.dist) return;
-  for (const std::string& gb : C.R.group_bys) {
-    if (qs.numgb_index(gb) >= 0 || !numeric_gb_candidate(C, qs, gb)) continue;
+// `cls`: [candidate][glob] classes -- this process's files, or what the ranks of a distributed call agreed on
+// (plan_globs), which every rank then decides alike and refuses with the same text.
+void decide_numeric_group_bys(const EvalCall& C, QueryShape& qs, const std::vector<std::string>& cands,
+                              const std::vector<GbClass>& cls) {
+  const size_t ng = glob_count(C);
+  const std::string over = C.dist ? ", over the ranks of this distributed evaluation" : "";
+  for (size_t ci = 0; ci < cands.size(); ci++) {
+    const std::string& gb = cands[ci];
     auto refuse = [&](const std::string& why) { throw PlanError(LK_ERR_UNSUPPORTED, "numeric groupBy: column " + gb + " " + why); };
     bool any_num = false, any_text = false;
     long text_glob = -1, num_glob = -1;
-    for (size_t i = 0; i < C.n_paths; i += size_t(C.glob_size)) {
-      bool text = false, num = false, boolean = false;
-      for (size_t j = i; j < std::min(C.n_paths, i + size_t(C.glob_size)); j++) {
-        if (!gp.segs[j]) continue;
-        const int c = gp.segs[j]->col_index(gb);
-        if (c < 0) continue;   // absent (NULLs), or of a type the loader does not decode (refused in plan_globs)
-        const HostCol& hc = gp.segs[j]->cols[size_t(c)];
-        if (hc.is_string) text = true;
-        else if (hc.ptype == pq::BOOLEAN) boolean = true;
-        else if (value_rank(hc.ptype)) num = true;
+    for (size_t gi = 0; gi < ng; gi++) {
+      const GbClass& c = cls[ci * ng + gi];
+      const std::string gs = std::to_string(gi);
+      switch (gb_class_union(c, nullptr)) {
+        case GB_TEXT_WITH_NUMBER: refuse("is VARCHAR in some files and numeric in others of glob " + gs + over); break;
+        case GB_BOOLEAN_WITH_NUMBER: refuse("is BOOLEAN in some files and numeric in others of glob " + gs + over); break;
+        case GB_OK: break;
       }
-      const std::string gs = std::to_string(i / size_t(C.glob_size));
-      // union_by_name of VARCHAR and a number is VARCHAR, the numbers printed by DuckDB's cast; BOOLEAN with a number
-      // does not unify as the numeric classes do
-      if (text && (num || boolean)) refuse("is VARCHAR in some files and numeric in others of glob " + gs);
-      if (boolean && num) refuse("is BOOLEAN in some files and numeric in others of glob " + gs);
-      if (text) any_text = true, text_glob = long(i / size_t(C.glob_size));
-      if (num || boolean) any_num = true, num_glob = long(i / size_t(C.glob_size));
+      if (c.text) any_text = true, text_glob = long(gi);
+      if (c.numeric()) any_num = true, num_glob = long(gi);
     }
     if (!any_num) continue;   // a string groupBy, or a column no loaded file has
     if (any_text)
-      refuse("is VARCHAR in glob " + std::to_string(text_glob) + " and numeric in glob " + std::to_string(num_glob) + " of the same call");
+      refuse("is VARCHAR in glob " + std::to_string(text_glob) + " and numeric in glob " + std::to_string(num_glob) + " of the same call" + over);
     if ((C.flags & kEvalMetricsPct) || (qs.ces && C.R.dataset == "metrics"))
       refuse("is numeric; metrics p<NN> / ces take no numeric groupBy");
     if (qs.numgbs.size() >= size_t(MAXND)) refuse("is numeric: more than " + std::to_string(MAXND) + " numeric groupBys");
@@ -370,6 +364,44 @@ void plan_numeric_group_bys(const EvalCall& C, QueryShape& qs, const GlobPlan& g
     if (std::find(qs.nums.begin(), qs.nums.end(), gb) == qs.nums.end()) qs.nums.push_back(gb);
     qs.numeric = true;   // every segment takes the general row scan
   }
+}
+
+// Before the filter's string columns are listed.  One process: decided from its loaded files.  Distributed: the classes
+// are agreed on in plan_globs, whose all-gather needs a filter plan first -- so this pass decides from the request alone
+// (every rank alike, no rank-local refusal ahead of the collective): a groupBy is taken as a string column, unless a
+// gt/ge/lt/le leaf reads it (plan_filter would refuse the column in both roles); evaluate_once plans again from the
+// agreed classes wherever they, or such a leaf, say the first pass may be wrong (dist_numeric_replan).
+void plan_numeric_group_bys(const EvalCall& C, QueryShape& qs, const GlobPlan& gp) {
+  const std::vector<std::string> cands = numeric_gb_candidates(C, qs);
+  if (C.dist) {
+    for (const std::string& gb : cands)
+      if (std::find(qs.nums.begin(), qs.nums.end(), gb) != qs.nums.end()) qs.numgbs.push_back(gb);
+    return;
+  }
+  const size_t ng = glob_count(C);
+  std::vector<GbClass> cls(cands.size() * ng);
+  for (size_t ci = 0; ci < cands.size(); ci++)
+    for (size_t j = 0; j < C.n_paths; j++)
+      if (gp.segs[j]) add_file_class(cls[ci * ng + j / size_t(C.glob_size)], *gp.segs[j], cands[ci]);
+  decide_numeric_group_bys(C, qs, cands, cls);
+}
+
+bool dist_numeric_replan(const EvalCall& C, const QueryShape& qs, const GlobPlan& gp) {
+  if (!C.dist) return false;
+  if (!qs.numgbs.empty()) return true;   // the first pass took a leafed groupBy as numeric: the files decide
+  return std::any_of(gp.gb_class.begin(), gp.gb_class.end(), [](const GbClass& c) { return c.numeric(); });
+}
+
+// The second pass of a distributed call: the loaded segments stay, everything plan_globs filled starts over.
+void reset_glob_plan(GlobPlan& gp) {
+  GlobPlan fresh;
+  fresh.world = gp.world;
+  fresh.rank = gp.rank;
+  fresh.segs = std::move(gp.segs);
+  fresh.seg_bad = std::move(gp.seg_bad);
+  fresh.bad_msg = std::move(gp.bad_msg);
+  fresh.tag_numeric = gp.tag_numeric;
+  gp = std::move(fresh);   // (releases the FieldTab lock the first pass may hold)
 }
 
 void plan_globs(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, GlobPlan& gp) {
@@ -393,10 +425,12 @@ void plan_globs(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, G
   const size_t np = gp.probe_cols.size();
   const size_t ng = gp.globs.size();
   // [.. | value NULLs | numeric tag column | globs: a numeric file of the chart field | globs: a VARCHAR file of it]
-  // [.. | a numeric groupBy column on some rank (distributed calls: refused, below)]
-  gp.exists.assign(ng * np + 2 * ng + 2 + 2 * ng + 1, 0);
+  // [.. | candidate groupBys x globs: the column's class over the glob's files, 3 bytes (GbClass)]
+  const std::vector<std::string> cands = numeric_gb_candidates(C, qs);
+  gp.exists.assign(ng * np + 2 * ng + 2 + 2 * ng + cands.size() * ng * kGbClassBytes, 0);
   const size_t vnull_at = ng * np + 2 * ng;
-  const size_t numgb_at = gp.exists.size() - 1;
+  const size_t gbclass_at = vnull_at + 2 + 2 * ng;
+  std::vector<GbClass> cls(cands.size() * ng);
   gp.num_ut.assign(qs.numgbs.size(), std::vector<int>(ng, -1));
   gp.exists[vnull_at + 1] = gp.tag_numeric ? 1 : 0;
   uint8_t* gfnum = gp.exists.data() + vnull_at + 2;
@@ -498,25 +532,38 @@ void plan_globs(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, G
         const int k = qs.numgb_index(nm);
         const int c = k >= 0 ? S.col_index(nm) : -1;
         if (c >= 0 && numeric_dim_type(S.cols[size_t(c)].ptype) && !S.cols[size_t(c)].is_string) {
-          // the group column's union_by_name type over the glob's files (BOOLEAN alone: plan_numeric_group_bys)
-          const int pt = S.cols[size_t(c)].ptype;
-          int& ut = gp.num_ut[size_t(k)][gi];
-          ut = (ut < 0 || pt == pq::BOOLEAN) ? pt : value_type_of_rank(std::max(value_rank(ut), value_rank(pt)));
           // a BOOLEAN group column binds; a comparison leaf on it stays a glob failure
+          const int pt = S.cols[size_t(c)].ptype;
           const bool leafed = std::any_of(qs.all_leaves.begin(), qs.all_leaves.end(), [&](const FilterNode* l) { return l->k == nm; });
           if (pt == pq::BOOLEAN && !leafed) continue;
         }
         if (bad(nm, 3)) gfail[gi] = 1;
       }
-      // distributed: which columns are numeric depends on each rank's segments -- the ranks agree on the refusal
-      if (C.dist)
-        for (auto& gb : fp.gbs) {
-          const int c = numeric_gb_candidate(C, qs, gb) ? S.col_index(gb) : -1;
-          if (c >= 0 && !S.cols[size_t(c)].is_string && numeric_dim_type(S.cols[size_t(c)].ptype)) gp.exists[numgb_at] = 1;
-        }
+      // which groupBys are numeric, and of which union type, depends on every rank's segments: the classes travel
+      // with the unions, and their element-wise max over the ranks is union_by_name
+      for (size_t ci = 0; ci < cands.size(); ci++) add_file_class(cls[ci * ng + gi], S, cands[ci]);
     }
+  for (size_t i = 0; i < cls.size(); i++) {
+    uint8_t* b = gp.exists.data() + gbclass_at + i * kGbClassBytes;
+    b[0] = cls[i].text, b[1] = cls[i].boolean, b[2] = cls[i].rank;
+  }
   // every rank sees every glob's union, failures and value type; a rank-local engine failure fails every rank here
   if (C.dist) comm_agree_max_u8(C.E, C.X, gp.load_err, gp.load_msg, gp.exists.data(), gp.exists.size());
+  for (size_t i = 0; i < cls.size(); i++) {
+    const uint8_t* b = gp.exists.data() + gbclass_at + i * kGbClassBytes;
+    cls[i] = GbClass{b[0], b[1], b[2]};
+  }
+  gp.gb_cands = cands;
+  gp.gb_class = cls;
+  // the numeric group columns' union_by_name type per glob, from the agreed classes alone: a rank holding only an INT32
+  // file of a glob whose DOUBLE file is another rank's keys and prints its values as DOUBLE
+  for (size_t k = 0; k < qs.numgbs.size(); k++) {
+    const size_t ci = size_t(std::find(cands.begin(), cands.end(), qs.numgbs[k]) - cands.begin());
+    for (size_t gi = 0; gi < ng && ci < cands.size(); gi++) {
+      int ut = -1;
+      if (gb_class_union(cls[ci * ng + gi], &ut) == GB_OK && ut != pq::BYTE_ARRAY) gp.num_ut[k][gi] = ut;
+    }
+  }
   gp.value_nulls = gp.exists[vnull_at] != 0;
   if (qs.fchart)
     for (size_t gi = 0; gi < ng; gi++) {
@@ -525,11 +572,6 @@ void plan_globs(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, G
         throw PlanError(LK_ERR_UNSUPPORTED, "field chart: column " + qs.vcol + " is numeric in some files and VARCHAR in others of glob " + std::to_string(gi));
       gp.ftext_any = gp.ftext_any || gftext[gi];
     }
-  if (gp.exists[numgb_at]) {   // (the same text on every rank)
-    std::string names;
-    for (auto& gb : fp.gbs) names += (names.empty() ? "" : ", ") + gb;
-    throw PlanError(LK_ERR_UNSUPPORTED, "numeric groupBy: a distributed evaluation takes no groupBy column stored as a number (groupBys: " + names + ")");
-  }
   gp.tag_numeric = gp.exists[vnull_at + 1] != 0;   // agreed: a numeric tag column on some rank
   if (gp.tag_numeric) return;
   for (size_t gi = 0; gi < ng; gi++)

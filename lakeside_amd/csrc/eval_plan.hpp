@@ -13,6 +13,7 @@
 #include "engine.hpp"
 #include "evalutil.hpp"
 #include "kernels.hpp"
+#include "numgroup_agree.hpp"
 #include "plan.hpp"
 
 namespace lk {
@@ -123,13 +124,17 @@ struct GlobPlan {
   std::set<std::string> fset;
   std::vector<std::string> probe_cols;   // columns whose existence matters
   // [globs x np exists | globs fail | globs value-type rank | value NULLs | numeric tag column |
-  //  globs: a numeric file of the chart field | globs: a VARCHAR file of it]
+  //  globs: a numeric file of the chart field | globs: a VARCHAR file of it |
+  //  candidate groupBys x globs: the column's class (GbClass, 3 bytes)]
   std::vector<uint8_t> exists;
   std::vector<GlobInfo> globs;
   bool value_nulls = false;
   bool ftext_any = false;     // field chart: some glob's chart field is VARCHAR
-  // numeric groupBys: [numgb][glob] the column's union_by_name type over the glob's files (Parquet type; -1: no file
-  // of the glob has it)
+  // the groupBys that may be numeric (the request alone decides) and [candidate][glob] their agreed classes
+  std::vector<std::string> gb_cands;
+  std::vector<GbClass> gb_class;
+  // numeric groupBys: [numgb][glob] the column's union_by_name type over the glob's files on every rank, from the
+  // agreed classes (Parquet type; -1: no file of the glob has it)
   std::vector<std::vector<int>> num_ut;
   size_t nfailed = 0;
   int64_t step = -1;
@@ -190,6 +195,8 @@ struct NumDimTables {
   uint64_t cap = 0;           // slots per (glob, column)
   int attempts = 0;
   double ms = 0;
+  double exchange_ms = 0;     // distributed: the value sets' all-gather and union (this rank)
+  uint64_t exchange_bytes = 0;
   unsigned long long* d_keys = nullptr;
   uint32_t* d_ids = nullptr;
   uint32_t* d_ones = nullptr;
@@ -246,6 +253,13 @@ void plan_filter(const EvalCall& C, const QueryShape& qs, FilterPlan& fp);
 void load_segments(const EvalCall& C, const QueryShape& qs, GlobPlan& gp);
 // Which groupBys are numeric group dimensions (reads the loaded segments' schemas; before plan_filter).
 void plan_numeric_group_bys(const EvalCall& C, QueryShape& qs, const GlobPlan& gp);
+// Distributed calls: the groupBys that may be numeric; whether the agreed classes of plan_globs ask for a second pass
+// (shape -> filter -> globs) and its decision from them, the same on every rank; the glob plan emptied for that pass.
+std::vector<std::string> numeric_gb_candidates(const EvalCall& C, const QueryShape& qs);
+bool dist_numeric_replan(const EvalCall& C, const QueryShape& qs, const GlobPlan& gp);
+void decide_numeric_group_bys(const EvalCall& C, QueryShape& qs, const std::vector<std::string>& cands,
+                              const std::vector<GbClass>& cls);
+void reset_glob_plan(GlobPlan& gp);
 void plan_globs(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, GlobPlan& gp);   // collective: globs
 void cell_policy(const EvalCall& C, const QueryShape& qs, const GlobPlan& gp, CellSpace& cs);
 void plan_dims(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, DimPlan& dp);     // collective: dims

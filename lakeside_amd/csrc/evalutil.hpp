@@ -124,8 +124,10 @@ LockedLeafBits extend_leaf_bits(Engine& E, const LeafCol& sc, const GlobalDict& 
 // Java 17 Double.toString / Float.toString text (jdtoa.cpp).
 std::string java_text(double d);
 std::string java_text(float f);
-// JDBC getString text of a raw value of Parquet physical type `pt` read as union_by_name type `ut` (exemplar.cpp).
+// JDBC getString text of a raw value of Parquet physical type `pt` read as union_by_name type `ut`; a raw 64-bit word
+// of type `ptype` as a double (numgroup_agree.cpp).
 std::string value_text(unsigned long long raw, int pt, int ut);
+double raw_as_double(unsigned long long raw, int ptype);
 // A test knob of the environment, read on every call (exemplar.cpp).
 uint64_t env_u64(const char* name, uint64_t dflt, uint64_t floor);
 

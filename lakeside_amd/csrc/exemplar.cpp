@@ -79,46 +79,6 @@ int union_type(int a, int b) {
 
 }  // namespace
 
-// A raw 64-bit word of Parquet physical type `ptype` as a double: DOUBLE / FLOAT bit patterns, INT32 / INT64 values.
-static double raw_as_double(unsigned long long raw, int ptype) {
-  switch (ptype) {
-    case pq::DOUBLE: {
-      double d;
-      memcpy(&d, &raw, 8);
-      return d;
-    }
-    case pq::INT64: return double(int64_t(raw));
-    case pq::INT32: return double(int32_t(uint32_t(raw)));
-    case pq::FLOAT: {
-      float f;
-      const uint32_t u = uint32_t(raw);
-      memcpy(&f, &u, 4);
-      return double(f);
-    }
-    default: throw PlanError(LK_ERR_UNSUPPORTED, "exemplar value column of a non-numeric type");
-  }
-}
-
-// JDBC getString text of a raw value of physical type `pt` read as union type `ut`.
-std::string value_text(unsigned long long raw, int pt, int ut) {
-  int64_t iv = 0;
-  float fv = 0.0f;
-  switch (pt) {
-    case pq::INT64: iv = int64_t(raw); fv = float(iv); break;
-    case pq::INT32: iv = int32_t(uint32_t(raw)); fv = float(iv); break;
-    case pq::DOUBLE: break;
-    case pq::FLOAT: fv = float(raw_as_double(raw, pt)); break;
-    case pq::BOOLEAN: return raw ? "true" : "false";
-    default: throw PlanError(LK_ERR_UNSUPPORTED, "exemplar column of an undecoded type");
-  }
-  switch (ut) {
-    case pq::INT64:
-    case pq::INT32: return std::to_string(iv);
-    case pq::FLOAT: return java_text(fv);
-    default: return java_text(raw_as_double(raw, pt));
-  }
-}
-
 // A test knob of the environment, read on every call (the tests change them between the calls of one process).
 uint64_t env_u64(const char* name, uint64_t dflt, uint64_t floor) {
   const char* e = getenv(name);
