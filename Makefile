@@ -18,11 +18,13 @@ HOST_OBJS = $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(HOST_SRCS))
 # the fused scan kernels: one unit per (aggregate, kernel family, table mode) so they compile in parallel
 SCAN_LEAN  = $(foreach a,sum min max count,$(foreach m,d h,$(OBJDIR)/scan_$(a)_lean_$(m).o))
 SCAN_TILES = $(foreach a,sum min max count,$(foreach m,d h,$(OBJDIR)/scan_$(a)_tiles_$(m).o))
-HIP_OBJS  = $(OBJDIR)/kernels.o $(OBJDIR)/ex_kernels.o $(OBJDIR)/formula_kernels.o $(SCAN_LEAN) $(SCAN_TILES)
+# scan_clu (the name-clustered value copy): SUM / MIN / MAX, dense tables only
+SCAN_CLU   = $(foreach a,sum min max,$(OBJDIR)/scan_$(a)_clu_d.o)
+HIP_OBJS  = $(OBJDIR)/kernels.o $(OBJDIR)/ex_kernels.o $(OBJDIR)/formula_kernels.o $(OBJDIR)/clu_kernels.o $(SCAN_LEAN) $(SCAN_TILES) $(SCAN_CLU)
 HDRS = $(wildcard $(SRC)/*.hpp) $(SRC)/unicode_tables.inc include/lakeside_gpu.h include/lakeside_regex.h include/lakeside_text.h
 # device code includes only these (host-only header edits do not rebuild the kernels); lean_kernel.hpp only the
 # scan_lean units, scan_kernel.hpp only the scan units
-DEV_HDRS = $(SRC)/device_common.hpp $(SRC)/kernels.hpp $(SRC)/layout.hpp $(SRC)/scan_inst.hpp $(SRC)/bucket.hpp
+DEV_HDRS = $(SRC)/device_common.hpp $(SRC)/kernels.hpp $(SRC)/layout.hpp $(SRC)/scan_inst.hpp $(SRC)/bucket.hpp $(SRC)/clu.hpp
 # the formula kernels: correctly rounded IEEE double, one operation at a time (no contraction; they use no atomics on
 # floating point, so -munsafe-fp-atomics selects nothing in this unit)
 $(OBJDIR)/formula_kernels.o: HIPFLAGS += -ffp-contract=off
@@ -40,6 +42,7 @@ $(OBJDIR)/%.o: $(SRC)/%.hip $(DEV_HDRS)
 
 $(SCAN_TILES): $(SRC)/scan_kernel.hpp
 $(SCAN_LEAN): $(SRC)/scan_kernel.hpp $(SRC)/lean_kernel.hpp
+$(SCAN_CLU): $(SRC)/clu_kernel.hpp
 
 $(LIB): $(HOST_OBJS) $(HIP_OBJS)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -o $@ $^ -L$(ROCM)/lib -lrccl -lz -l:libzstd.so.1 -l:liblz4.so.1 -l:libbrotlidec.so.1 -Wl,-rpath,$(ROCM)/lib
@@ -51,7 +54,7 @@ $(RELIB): $(SRC)/regex.cpp $(SRC)/regex_capi.cpp $(SRC)/regex.hpp $(SRC)/unicode
 # host-only Java 17 number text, the field charts' text -> double classifier and the formula parser / cell function
 # (CPU differential tests); the filter planning (filter_plan.cpp) with the request parser, numeric literals and regex
 # compiler it calls; the numeric groupBys' rules over agreed data (numgroup_agree.cpp)
-TX_SRCS = $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/ex_select_sim.cpp $(SRC)/bucket_sim.cpp $(SRC)/filter_plan.cpp $(SRC)/filter_plan_sim.cpp $(SRC)/plan.cpp $(SRC)/numleaf.cpp $(SRC)/regex.cpp $(SRC)/numgroup_agree.cpp
+TX_SRCS = $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/ex_select_sim.cpp $(SRC)/bucket_sim.cpp $(SRC)/clu_sim.cpp $(SRC)/filter_plan.cpp $(SRC)/filter_plan_sim.cpp $(SRC)/plan.cpp $(SRC)/numleaf.cpp $(SRC)/regex.cpp $(SRC)/numgroup_agree.cpp
 $(TXLIB): $(TX_SRCS) $(HDRS)
 	g++ $(CXXFLAGS_HOST) -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -shared -o $@ $(TX_SRCS)
 
@@ -82,10 +85,10 @@ all: $(CPULIB)
 # selected with LK_LIB_PATH.
 EXP_FLAGS ?=
 EXP_NAME ?= x
-exp: $(HOST_OBJS) $(OBJDIR)/kernels.o $(OBJDIR)/ex_kernels.o $(SCAN_TILES)
+exp: $(HOST_OBJS) $(OBJDIR)/kernels.o $(OBJDIR)/ex_kernels.o $(OBJDIR)/formula_kernels.o $(OBJDIR)/clu_kernels.o $(SCAN_TILES) $(SCAN_CLU)
 	@mkdir -p build/exp/$(EXP_NAME) lakeside_amd/exp
 	for a in sum min max count; do for m in d h; do $(HIPCC) $(HIPFLAGS) $(EXP_FLAGS) -c $(SRC)/scan_$${a}_lean_$${m}.hip -o build/exp/$(EXP_NAME)/scan_$${a}_lean_$${m}.o & done; done; wait
-	$(HIPCC) -shared --offload-arch=$(ARCH) -o lakeside_amd/exp/liblakeside_gpu_$(EXP_NAME).so $(HOST_OBJS) $(OBJDIR)/kernels.o $(OBJDIR)/ex_kernels.o $(SCAN_TILES) build/exp/$(EXP_NAME)/scan_*.o -L$(ROCM)/lib -lrccl -lz -l:libzstd.so.1 -l:liblz4.so.1 -l:libbrotlidec.so.1 -Wl,-rpath,$(ROCM)/lib
+	$(HIPCC) -shared --offload-arch=$(ARCH) -o lakeside_amd/exp/liblakeside_gpu_$(EXP_NAME).so $(HOST_OBJS) $(OBJDIR)/kernels.o $(OBJDIR)/ex_kernels.o $(OBJDIR)/formula_kernels.o $(OBJDIR)/clu_kernels.o $(SCAN_TILES) $(SCAN_CLU) build/exp/$(EXP_NAME)/scan_*.o -L$(ROCM)/lib -lrccl -lz -l:libzstd.so.1 -l:liblz4.so.1 -l:libbrotlidec.so.1 -Wl,-rpath,$(ROCM)/lib
 .PHONY: exp
 
 # Host-only loader harness (no HIP): the Parquet walk, dictionary interning and staging copy of lakeside_amd/csrc/

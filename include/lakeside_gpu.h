@@ -50,7 +50,8 @@ enum {
                                  (lk_result_stats "plan_bytes"; measurement only, costs ~5% of scan time) */
 
 /* options_json: {"device": 0, "hbm_budget_bytes": N, "max_calls": 4, "dict_compact_min_dead": 1024,
- *                "load_threads": 0, "formula_dense_max_cells": 4194304, "formula_hash_slots": 0}; NULL = defaults.
+ *                "load_threads": 0, "formula_dense_max_cells": 4194304, "formula_hash_slots": 0,
+ *                "cluster_values": true}; NULL = defaults.
  * hbm_budget_bytes: weight bound of the HBM segment cache (the worker's Caffeine cache weight,
  * query-worker/.../WorkerApi.scala:53-64): inserting past it evicts least-recently-used segments; 0 (default) = no
  * bound, eviction only when HBM runs out.  max_calls: evaluations in flight (one stream each).
@@ -59,6 +60,9 @@ enum {
  * the live ids densely first, so group-dim spaces track the cached segments (results keep their strings).
  * load_threads: host threads of a segment load (page walk, decompression, staging copies); 0 (default) = the
  * process's OMP_NUM_THREADS share of the host's cores, at most 16.
+ * cluster_values: a load also keeps, per tile, a copy of `_cardinalhq.value` grouped by `_cardinalhq.name` code (10 B
+ * per row of eligible tiles, counted in the cache weight), which name-filtered SUM / MIN / MAX queries stream instead of
+ * gathering values row by row; false = no copy, for deployments that prefer the cache capacity.
  * Replaces DuckDbConnectionFactory (core/.../utils/DuckDbConnectionFactory.scala:76-114). */
 int lk_engine_create(const char* options_json, lk_engine** out);
 void lk_engine_destroy(lk_engine* e);
@@ -73,7 +77,9 @@ int lk_segment_evict(lk_engine* e, const char* key);
 size_t lk_segment_count(const lk_engine* e);
 /* HBM bytes held by the cache. */
 size_t lk_segment_bytes(const lk_engine* e);
-/* Engine counters as JSON: {"segments", "segment_bytes", "evictions", "dict_compactions",
+/* Engine counters as JSON: {"segments", "segment_bytes", "clu_bytes" (the clustered value copies' share),
+ * "clu_alloc_failed" (loads whose copy could not be allocated: those segments serve the other kernels), "evictions",
+ * "dict_compactions",
  * "dictionaries": {column: {"size", "live", "generation"}}}; valid until the calling thread's next call. */
 const char* lk_engine_stats(lk_engine* e);
 /* Drops the engine's per-query caches -- parsed requests, per-(column, leaf) dictionary outcomes, value-key orders,

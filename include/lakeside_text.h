@@ -50,6 +50,16 @@ int lk_ex_select_sim(const int64_t* ts, size_t n, int64_t win_lo, int64_t win_hi
 void lk_bucket_sim(const int64_t* ts, size_t n, int64_t win_lo, int64_t win_hi, int64_t step, int64_t base,
                    uint64_t nbuckets, int metrics, int fast_div, int64_t* bucket, uint8_t* status, int64_t* mono);
 
+/* Runs the name-clustered value copy's tile rule (lakeside_amd/csrc/clu.hpp, clu_classify as scan_clu inlines it) over
+ * n tiles given by their timestamp zone maps and sorted flags: kind[i] = 0 outside the window, 1 pinned to bucket b0[i],
+ * 2 split (nsb[i] class boundaries, first bucket b0[i]), 3 inside the window but not taken.  lk_clu_segment_taken is
+ * the host's rule for a whole segment (every tile has a copy and sorted timestamps; `widest` = the largest
+ * ts_max - ts_min of its tiles): 1 when scan_clu takes the segment, so scan_lean need not run over it. */
+void lk_clu_sim(const int64_t* ts_min, const int64_t* ts_max, const uint8_t* sorted, size_t n, int64_t win_lo,
+                int64_t win_hi, int64_t step, int64_t base, uint64_t nbuckets, int split_ok, uint8_t* kind, int64_t* b0,
+                uint32_t* nsb);
+int lk_clu_segment_taken(int all_copies_sorted, int64_t widest, int64_t step);
+
 /* Plans the filter of a PushDownRequest as the evaluator does before it reads a segment (lakeside_amd/csrc/
  * filter_plan.cpp: the leaf loop of the shape gate, plan_filter, plan_truth); numeric_group_bys[0..n) are the groupBys
  * to take as columns stored as numbers (the evaluator learns them from the loaded files).  Writes a JSON object into out

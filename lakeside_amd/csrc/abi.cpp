@@ -66,6 +66,7 @@ int lk_engine_create(const char* options_json, lk_engine** out) {
       if (options_json && *options_json) {
         lk::Json o = lk::Json::parse(options_json);
         if (const lk::Json* b = o.get("hbm_budget_bytes")) e->e->hbm_budget = size_t(b->as_i64());
+        if (const lk::Json* c = o.get("cluster_values")) e->e->cluster_values = c->as_bool();
         if (const lk::Json* c = o.get("max_calls")) e->e->max_calls = size_t(std::max<int64_t>(1, c->as_i64()));
         if (const lk::Json* d = o.get("dict_compact_min_dead"))
           e->e->compact_min_dead = size_t(std::max<int64_t>(1, d->as_i64()));
@@ -118,7 +119,7 @@ int lk_segment_evict(lk_engine* e, const char* key) {
       e->e->evicted_puts.erase(key);   // the caller dropped the key itself
       auto it = e->e->cache.find(key);
       if (it == e->e->cache.end()) return int(LK_ERR_ARG);
-      e->e->cache_bytes -= it->second->data_bytes + it->second->meta_bytes;
+      e->e->cache_bytes -= it->second->hbm_bytes();
       victim = std::move(it->second);
       e->e->cache.erase(it);
     }
@@ -135,6 +136,9 @@ const char* lk_engine_stats(lk_engine* e) {
     o += "\"segments\":" + std::to_string(E.cache.size()) + ",\"segment_bytes\":" + std::to_string(E.cache_bytes) +
          ",\"evictions\":" + std::to_string(E.evictions) + ",\"load_ms\":" + std::to_string(E.load_ms_total) +
          ",\"load_host_ms\":" + std::to_string(E.load_host_ms_total);
+    size_t clu = 0;   // the clustered value copies' share of segment_bytes
+    for (auto& kv : E.cache) clu += kv.second->clu_bytes;
+    o += ",\"clu_bytes\":" + std::to_string(clu) + ",\"clu_alloc_failed\":" + std::to_string(E.clu_alloc_failed.load());
   }
   o += ",\"dict_compactions\":" + std::to_string(E.compactions) + ",\"dictionaries\":{";
   {

@@ -1,0 +1,255 @@
+// scan_clu<AGG> (SUM, MIN, MAX; dense tables): the name-filter scan over the name-clustered value copy (layout.hpp,
+// CluTile; built at load by clu_build, clu_kernels.hip).  Included by the scan_<agg>_clu_d.hip units through
+// scan_inst.hpp.  The host (eval_plan.cpp, plan_cluster) hands it the segments whose every tile clu_tile takes, so
+// neither scan_lean nor scan_tiles runs over them.
+//
+// Per tile: the passing-code mask exactly as scan_lean computes it (remap -> strtab -> T / F bits -> truth word,
+// leaf_false included), then for each passing code c the contiguous range cvals[cpref[c] .. cpref[c + 1]) streamed
+// with coalesced 8-B loads.  A pinned tile's elements all land in one bucket; a split tile also streams crows (the
+// element's row within the tile) and takes each element's class from its row index against boundary rows found with
+// scan_lean's two-round timestamp search (256 samples, then the sample gap holding each boundary).  No run staging,
+// no chunk table, no row list, no LDS: the wave reduces per (code, class) and lane 0 merges once per (tile, code,
+// class) through global_merge, which honours the LEAN_* flags, the -0.0 empty marker, exact_sum and FLAG_MIN_NAN.
+//
+// Shape: one wave per tile, four tiles per 256-thread workgroup, no barrier.  C2's tile has about 4,096 passing values
+// (32 KB): a wave holds 16 loads per lane (8 KB) in flight, and 16 waves per CU keep 128 KB per CU in flight -- the
+// stream is latency-bound, so what counts is bytes in flight per CU, and a wave per tile needs no cross-wave reduction
+// (one merge per (tile, code, class) as it stands).  Measured in this shape: C2's scan 1.114 -> 0.163 ms,
+// c2s10 1.206 -> 0.250 ms, dense (all 16 codes pass) 2.434 -> 1.733 ms.  A workgroup per tile and several tiles per
+// wave were not measured (DESIGN §9 lists the comparison as open).
+#pragma once
+#include <type_traits>
+
+#include "clu.hpp"
+#include "device_common.hpp"
+
+namespace lk {
+
+constexpr int CLU_WAVES = BLOCK / 64;   // tiles per workgroup
+
+template <int AGG>
+__global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
+  static_assert(AGG == AGG_SUM || AGG == AGG_MIN || AGG == AGG_MAX, "scan_clu: SUM, MIN, MAX");
+  const uint32_t lane = threadIdx.x & 63u;
+  const QSeg* Sp = P.segs + blockIdx.y;
+  const uint32_t t = uni(blockIdx.x * uint32_t(CLU_WAVES) + (threadIdx.x >> 6));
+  if (t >= Sp->ntiles) return;
+  const TileDesc* tdp = Sp->tiles + t;
+  const CluClass cc = clu_tile(P, Sp, t);
+  if (cc.kind == CLU_NONE) return;   // zone map: outside the glob window
+  if (cc.kind == CLU_UNTAKEN) {      // the host hands over only segments whose tiles are all taken (clu_segment_taken)
+    if (lane == 0) atomicOr(P.flags, FLAG_CELL_RANGE);
+    return;
+  }
+  const CluTile d = Sp->clu[t];
+  const TileCol* tc0 = Sp->cols[0].tcols + t;
+  const TileCol* tc2 = Sp->cols[2].tcols + t;
+  const uint32_t nrows = d.nrows < tdp->nrows ? d.nrows : tdp->nrows;
+  const uint32_t dict_n = tc2->dict_n < 64u ? tc2->dict_n : 64u;
+  const bool count_plan = P.plan_bytes != nullptr;
+  uint64_t pbytes = 0;
+
+  // passing codes: one ballot over the chunk dictionary (Kleene: the leaves' T/F bits of the code), as scan_lean
+  uint32_t lut = 0;
+  bool pass = false;
+  if (lane < dict_n) {
+    const uint32_t g = (Sp->cols[2].remap + tc2->remap)[lane];
+    const uint32_t* tab = P.strp[0].strtab;
+    lut = tab ? tab[g] : g;
+    const uint32_t lf = Sp->leaf_false;
+    const uint32_t bits = (lut >> 24) << P.strp[0].lbase;
+    const uint32_t lmask = P.strp[0].lmask;
+    const uint32_t T = bits & lmask & ~lf, F = (~bits & lmask) | lf;
+    const uint32_t ix = T | (F << P.nleaves);
+    pass = (P.truth[ix >> 5] >> (ix & 31)) & 1u;
+  }
+  unsigned long long emask = __ballot(pass);
+  if (count_plan && lane == 0) {
+    atomicAdd(P.flags + 1, 1u);   // clustered_tiles
+    pbytes += sizeof(TileDesc) + sizeof(CluTile) + sizeof(TileCol) + uint64_t(dict_n) * 8u +
+              uint64_t((((1u << (2 * P.nleaves)) + 31) / 32) * 4u);
+  }
+  if (!emask) {   // no row of the tile passes
+    if (pbytes) atomicAdd(P.plan_bytes, (unsigned long long)pbytes);
+    return;
+  }
+
+  const uint8_t* blk = Sp->clu_base + d.off;
+  uint32_t cs, ce;   // lane c: the code's range [cs, ce) of cvals / crows
+  {
+    const uint32_t* cp = reinterpret_cast<const uint32_t*>(blk);
+    cs = cp[lane];
+    ce = cp[lane + 1u];
+    ce = ce < nrows ? ce : nrows;
+    cs = cs < ce ? cs : ce;
+    if (count_plan && lane == 0) pbytes += uint64_t(dict_n + 1u) * 4u;
+  }
+  const __amdgpu_buffer_rsrc_t rv = make_rsrc(blk + CLU_PREF_BYTES, nrows * 8u);
+  const uint16_t* crows = reinterpret_cast<const uint16_t*>(blk + CLU_PREF_BYTES + size_t(nrows) * 8u);
+
+  // split tiles: boundary rows (scan_lean's search, per wave: four samples / gap rows per lane)
+  const bool split = cc.kind == CLU_SPLIT;
+  const uint32_t nsb = cc.nsb;
+  uint32_t sb[CLU_SPLIT_MAX];
+#pragma unroll
+  for (uint32_t k = 0; k < CLU_SPLIT_MAX; k++) sb[k] = 0xffffffffu;
+  if (split) {   // uniform
+    const int64_t win_lo = Sp->win_lo, win_hi = Sp->win_hi;
+    const __amdgpu_buffer_rsrc_t rst = make_rsrc(Sp->base + tc0->vals, tc0->vals_len);
+    const uint32_t vbt = tc0->vbase;
+    auto cls_of = [&](int64_t ts) __attribute__((always_inline)) -> uint32_t {
+      if (ts < win_lo) return 0u;
+      if (ts >= win_hi) return nsb;
+      return uint32_t(bucket_mono(ts, P.step, P.bucket_base, false) - cc.b0) + 1u;
+    };
+    auto sample = [&](uint32_t s) __attribute__((always_inline)) -> uint32_t {   // row of sample s (s = 256: nrows)
+      return uint32_t((uint64_t(s) * nrows) >> 8);
+    };
+    auto ts_at = [&](uint32_t r, bool live) __attribute__((always_inline)) -> int64_t {
+      const v2u x = __builtin_amdgcn_raw_buffer_load_b64(rst, live ? (vbt + r) * 8u : OOB, 0, 0);
+      return int64_t(((uint64_t)x.y << 32) | x.x);
+    };
+    uint32_t scnt[CLU_SPLIT_MAX];   // per class boundary k: the samples below class k + 1 (uniform)
+#pragma unroll
+    for (uint32_t k = 0; k < CLU_SPLIT_MAX; k++) scnt[k] = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+      const uint32_t c = cls_of(ts_at(sample(lane + 64u * j), true));
+#pragma unroll
+      for (uint32_t k = 0; k < CLU_SPLIT_MAX; k++)
+        if (k < nsb) scnt[k] += uint32_t(__popcll(__ballot(c < k + 1u)));
+    }
+    // boundary k + 1 lies in the sample gap (sample(n - 1), sample(n)] (n samples below it; none: row 0)
+#pragma unroll
+    for (uint32_t k = 0; k < CLU_SPLIT_MAX; k++) {
+      if (k >= nsb) continue;
+      const uint32_t n = scnt[k];
+      uint32_t b = 0u;
+      if (n != 0u) {   // uniform
+        const uint32_t lo = sample(n - 1u) + 1u, hi = sample(n);
+        b = hi;   // the first sample at or above the class (n = 256: nrows, no such row)
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+          const uint32_t r = lo + lane + 64u * j;
+          const bool live = r < hi;
+          const bool f = cls_of(ts_at(r, live)) >= k + 1u && live;
+          const unsigned long long bl = __ballot(f);
+          if (bl) {
+            const uint32_t first = lo + 64u * j + uint32_t(__builtin_ctzll(bl));
+            b = first < b ? first : b;
+          }
+        }
+      }
+      sb[k] = b;
+    }
+    if (count_plan && lane == 0) pbytes += sizeof(TileCol) + 128u * (256u / 16u + nsb * 2u);   // sample and gap lines (approx.)
+  }
+  auto split_class = [&](uint32_t r) __attribute__((always_inline)) -> uint32_t {
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < CLU_SPLIT_MAX; k++) c += r >= sb[k] ? 1u : 0u;
+    return c;
+  };
+
+  const uint32_t stride = P.strp[0].dim_stride;
+  const unsigned long long glob_base = (unsigned long long)Sp->glob_slot * P.nbuckets;
+  bool nan_seen = false;
+
+  // One passing code's range [s, s + n): NK classes (pinned: 1, every element in bucket b0; split: the in-window
+  // classes 1 .. nsb - 1, at most CLU_SPLIT_MAX - 1), U loads per lane in flight
+  auto stream = [&](auto nkc, auto uc, uint32_t s, uint32_t n, uint32_t dim) __attribute__((always_inline)) {
+    constexpr uint32_t NK = decltype(nkc)::value;
+    constexpr uint32_t U = decltype(uc)::value;
+    constexpr bool SPLIT = NK > 1;
+    double hi[NK], lo[NK];
+    unsigned long long ext[NK];
+    uint32_t cnt[NK];
+#pragma unroll
+    for (uint32_t k = 0; k < NK; k++) {
+      hi[k] = lo[k] = 0.0;
+      ext[k] = AGG == AGG_MIN ? ~0ull : 0ull;
+      cnt[k] = 0u;
+    }
+    for (uint32_t i0 = 0; i0 < n; i0 += 64u * U) {
+      v2u x[U];
+      uint32_t r[U];
+#pragma unroll
+      for (uint32_t u = 0; u < U; u++) {
+        const uint32_t i = i0 + 64u * u + lane;
+        x[u] = __builtin_amdgcn_raw_buffer_load_b64(rv, i < n ? (s + i) * 8u : OOB, 0, 0);
+        r[u] = (SPLIT && i < n) ? uint32_t(crows[s + i]) : 0u;
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < U; u++) {
+        const uint32_t i = i0 + 64u * u + lane;
+        const double v = __longlong_as_double((long long)(((uint64_t)x[u].y << 32) | x[u].x));
+        const uint32_t c = SPLIT ? split_class(r[u]) : 1u;
+        const bool live = i < n;
+#pragma unroll
+        for (uint32_t k = 0; k < NK; k++) {
+          if (!live || c != k + 1u || (SPLIT && k + 1u >= nsb)) continue;
+          cnt[k] += 1u;
+          if (AGG == AGG_SUM) {
+            if (P.exact_sum) {
+              hi[k] += v;
+            } else {
+              double sm, e;
+              two_sum(hi[k], v, sm, e);
+              hi[k] = sm;
+              lo[k] += e;
+            }
+          } else {
+            if (AGG == AGG_MIN && v != v) nan_seen = true;
+            const unsigned long long o = dbl_order(v);
+            ext[k] = AGG == AGG_MIN ? (o < ext[k] ? o : ext[k]) : (o > ext[k] ? o : ext[k]);
+          }
+        }
+      }
+    }
+    // wave reduction per class, one merge per (tile, code, class)
+#pragma unroll
+    for (uint32_t k = 0; k < NK; k++) {
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        cnt[k] += __shfl_xor(cnt[k], off, 64);
+        if (AGG == AGG_SUM) {
+          const double oh = __shfl_xor(hi[k], off, 64);
+          if (P.exact_sum) {
+            hi[k] += oh;
+          } else {
+            const double ol = __shfl_xor(lo[k], off, 64);
+            double sm, e;
+            two_sum(hi[k], oh, sm, e);
+            hi[k] = sm;
+            lo[k] = lo[k] + ol + e;
+          }
+        } else {
+          const unsigned long long o = __shfl_xor(ext[k], off, 64);
+          ext[k] = AGG == AGG_MIN ? (o < ext[k] ? o : ext[k]) : (o > ext[k] ? o : ext[k]);
+        }
+      }
+      if (lane == 0 && cnt[k]) {
+        const unsigned long long cell = (glob_base + (unsigned long long)(cc.b0 + int64_t(k))) * P.ngroups + dim;
+        global_merge<AGG, false>(P, cell, cnt[k], cnt[k], hi[k], lo[k], ext[k]);
+      }
+    }
+    if (count_plan && lane == 0) {   // the 128-B lines of the streamed ranges
+      pbytes += 128u * uint64_t((((s + n) * 8u + 127u) >> 7) - ((s * 8u) >> 7));
+      if (SPLIT) pbytes += 128u * uint64_t((((s + n) * 2u + 127u) >> 7) - ((s * 2u) >> 7));
+    }
+  };
+
+  while (emask) {
+    const uint32_t c = uint32_t(__builtin_ctzll(emask));
+    emask &= emask - 1ull;
+    const uint32_t s = uni(__shfl(cs, int(c), 64)), e = uni(__shfl(ce, int(c), 64));
+    if (s >= e) continue;   // the name is absent from the tile
+    const uint32_t dim = (uni(__shfl(lut, int(c), 64)) & DIM_MASK) * stride;
+    if (split) stream(std::integral_constant<uint32_t, CLU_SPLIT_MAX - 1u>{}, std::integral_constant<uint32_t, 8u>{}, s, e - s, dim);
+    else stream(std::integral_constant<uint32_t, 1u>{}, std::integral_constant<uint32_t, 16u>{}, s, e - s, dim);
+  }
+  if (AGG == AGG_MIN && __ballot(nan_seen) && lane == 0) atomicOr(P.flags, FLAG_MIN_NAN);
+  if (pbytes) atomicAdd(P.plan_bytes, (unsigned long long)pbytes);
+}
+
+}  // namespace lk

@@ -1,0 +1,119 @@
+// clu_build: the name-clustered value copy of a segment's eligible tiles (layout.hpp, CluTile), built once at load on
+// the load stream (Engine::build_segment) from the name codes and values already in HBM.  One workgroup per tile: a
+// stable counting sort of the tile's rows by chunk-dictionary code -- codes ascending, rows ascending within a code, so
+// the layout is deterministic.  Not a hot kernel: every row's code is decoded twice (histogram, then placement), and a
+// 256-row step ranks its rows by ballot within the wave and through per-wave counts in LDS across waves.
+// Every global store is clamped to the tile's block, every stream read goes through a buffer resource.
+#include <hip/hip_runtime.h>
+
+#include "device_common.hpp"
+#include "kernels.hpp"
+
+namespace lk {
+namespace {
+
+__global__ __launch_bounds__(BLOCK) void clu_build(CluBuild B) {
+  constexpr uint32_t NW = BLOCK / 64;
+  __shared__ LRun runs[RUN_CAP];
+  __shared__ uint32_t next[64];        // histogram, then the next output position of every code
+  __shared__ uint32_t wcnt[NW][64];    // the step's rows per (wave, code)
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+  const uint32_t t = blockIdx.x;
+  if (t >= B.ntiles) return;
+  const CluTile d = B.desc[t];
+  if (d.off == CLU_NO_COPY) return;    // uniform
+  const TileCol* tn = B.name_tc + t;
+  const TileCol* tv = B.val_tc + t;
+  const uint32_t nrows = d.nrows < TILE_ROWS ? d.nrows : TILE_ROWS;
+  const uint32_t dict_n = d.dict_n < 1u ? 1u : (d.dict_n > 64u ? 64u : d.dict_n);
+  const uint32_t nr = tn->nruns < RUN_CAP ? tn->nruns : RUN_CAP;
+  const int bw = int(tn->bw);
+  const uint32_t vbn = tn->vbase, vbv = tv->vbase;
+  const __amdgpu_buffer_rsrc_t rn = make_rsrc(B.base + tn->vals, tn->vals_len + 8u);   // (as every hybrid_get_buf caller)
+  const __amdgpu_buffer_rsrc_t rvv = make_rsrc(B.base + tv->vals, tv->vals_len);
+  uint8_t* blk = B.clu + d.off;
+  uint32_t* cpref = reinterpret_cast<uint32_t*>(blk);
+  unsigned long long* cvals = reinterpret_cast<unsigned long long*>(blk + CLU_PREF_BYTES);
+  uint16_t* crows = reinterpret_cast<uint16_t*>(blk + CLU_PREF_BYTES + size_t(nrows) * 8u);
+
+  for (uint32_t i = tid; i < nr; i += BLOCK) {
+    const RunDesc r = B.name_runs[tn->run_lo + i];
+    runs[i] = LRun{r.start, r.off_lit, r.value};
+  }
+  if (tid < 64u) next[tid] = 0u;
+  for (uint32_t i = tid; i < NW * 64u; i += BLOCK) (&wcnt[0][0])[i] = 0u;
+  __syncthreads();
+  if (nr == 0u) return;                // uniform (an eligible tile has runs)
+  auto code_of = [&](uint32_t r) __attribute__((always_inline)) -> uint32_t {
+    const uint32_t v = vbn + r;
+    const uint32_t c = hybrid_get_buf(rn, runs[find_run(runs, int(nr), v)], v, bw);
+    return c < dict_n ? c : dict_n - 1u;   // (codes were validated against the dictionary at load)
+  };
+
+  // pass 1: rows per code, then the exclusive prefix (cpref[c] = first element of code c; cpref[64] = rows)
+  for (uint32_t r = tid; r < nrows; r += BLOCK) atomicAdd(&next[code_of(r)], 1u);
+  __syncthreads();
+  if (w == 0u) {
+    const uint32_t n = next[lane];
+    uint32_t inc = n;
+#pragma unroll
+    for (int dd = 1; dd < 64; dd <<= 1) {
+      const uint32_t o = __shfl_up(inc, dd, 64);
+      if (int(lane) >= dd) inc += o;
+    }
+    next[lane] = inc - n;
+    cpref[lane] = inc - n;
+    if (lane == 63u) cpref[64] = inc;
+  }
+  __syncthreads();
+
+  // pass 2: 256 rows per step, in row order
+  for (uint32_t r0 = 0; r0 < nrows; r0 += BLOCK) {
+    const uint32_t r = r0 + tid;
+    const bool valid = r < nrows;
+    const uint32_t c = valid ? code_of(r) : 0u;
+    const v2u x = __builtin_amdgcn_raw_buffer_load_b64(rvv, valid ? (vbv + r) * 8u : OOB, 0, 0);
+    uint32_t rank = 0;
+    unsigned long long rem = __ballot(valid);
+    while (rem) {   // uniform: one trip per distinct code of the wave's rows
+      const int l = __builtin_ctzll(rem);
+      const uint32_t cl = uint32_t(__shfl(int(c), l, 64));
+      const unsigned long long m = __ballot(valid && c == cl);
+      if (valid && c == cl) {
+        rank = uint32_t(__popcll(m & ((1ull << lane) - 1ull)));
+        if (int(lane) == l) wcnt[w][cl] = uint32_t(__popcll(m));
+      }
+      rem &= ~m;
+    }
+    __syncthreads();
+    if (valid) {
+      uint32_t pos = next[c] + rank;
+      for (uint32_t ww = 0; ww < w; ww++) pos += wcnt[ww][c];
+      if (pos < nrows) {
+        cvals[pos] = ((unsigned long long)x.y << 32) | x.x;
+        crows[pos] = uint16_t(r);
+      }
+    }
+    __syncthreads();
+    if (tid < 64u) {
+      uint32_t s = 0;
+#pragma unroll
+      for (uint32_t ww = 0; ww < NW; ww++) {
+        s += wcnt[ww][tid];
+        wcnt[ww][tid] = 0u;
+      }
+      next[tid] += s;
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+hipError_t launch_clu_build(const CluBuild& B, hipStream_t st) {
+  if (B.ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(clu_build, dim3(B.ntiles), dim3(BLOCK), 0, st, B);
+  return hipGetLastError();
+}
+
+}  // namespace lk

@@ -1,0 +1,20 @@
+// Host-only test hook (include/lakeside_text.h): the clustered copy's tile rule of clu.hpp as scan_clu and the host
+// call it.
+#include "../../include/lakeside_text.h"
+#include "clu.hpp"
+
+extern "C" void lk_clu_sim(const int64_t* ts_min, const int64_t* ts_max, const uint8_t* sorted, size_t n, int64_t win_lo,
+                           int64_t win_hi, int64_t step, int64_t base, uint64_t nbuckets, int split_ok, uint8_t* kind,
+                           int64_t* b0, uint32_t* nsb) {
+  using namespace lk;
+  for (size_t i = 0; i < n; i++) {
+    const CluClass c = clu_classify(ts_min[i], ts_max[i], win_lo, win_hi, step, base, nbuckets, sorted[i] != 0, split_ok != 0);
+    kind[i] = uint8_t(c.kind);
+    b0[i] = c.b0;
+    nsb[i] = c.nsb;
+  }
+}
+
+extern "C" int lk_clu_segment_taken(int all_copies_sorted, int64_t widest, int64_t step) {
+  return lk::clu_segment_taken(all_copies_sorted != 0, widest, step) ? 1 : 0;
+}

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "clu.hpp"
 #include "kernels.hpp"
 #include "layout.hpp"
 
@@ -220,6 +221,21 @@ __device__ __forceinline__ bool lean_tile(const QSeg* Sp, uint32_t t, uint32_t n
     if (l->has_nulls || l->kind != PAGE_DICT || l->nruns == 0u || l->bw > 32u) return false;
   }
   return true;
+}
+
+// The tile is scan_clu's (uniform: scalar loads): a lean tile (no late column) of a segment that carries the clustered
+// copy, with a copy of its own, whose rows get their bucket without a timestamp per row -- pinned by the zone map or
+// split (clu.hpp, clu_classify).  CLU_NONE: outside the glob window; CLU_UNTAKEN: another kernel's tile.  The host
+// applies the same rule per segment (clu_segment_taken) and hands scan_clu only segments it takes whole, so scan_lean
+// and scan_tiles, which do not see those segments, need no test of their own.
+__device__ __forceinline__ CluClass clu_tile(const QParams& P, const QSeg* Sp, uint32_t t) {
+  const TileDesc* td = Sp->tiles + t;
+  if (td->ts_max < Sp->win_lo || td->ts_min >= Sp->win_hi) return CluClass{CLU_NONE, 0, 0u};
+  if (!Sp->clu || Sp->clu[t].off == CLU_NO_COPY || P.metrics || P.hkeys || P.nstr != 1u || P.nvl || !P.truth ||
+      !lean_tile(Sp, t, 0u, 0u))
+    return CluClass{CLU_UNTAKEN, 0, 0u};
+  return clu_classify(td->ts_min, td->ts_max, Sp->win_lo, Sp->win_hi, P.step, P.bucket_base, P.nbuckets,
+                      (td->pad & TILE_TS_SORTED) != 0u, P.split_ok != 0u);
 }
 
 }  // namespace lk

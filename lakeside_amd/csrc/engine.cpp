@@ -451,6 +451,7 @@ Segment::~Segment() {
     }
   if (d_data) (void)hipFree(d_data);
   if (d_meta) (void)hipFree(d_meta);
+  if (d_clu) (void)hipFree(d_clu);
 }
 
 int Engine::load_thread_count() const {
@@ -531,6 +532,7 @@ std::shared_ptr<Segment> Engine::build_segment(const std::string& key, const uin
   }
   HIP_CHECK(hipMemcpyAsync(S->d_meta, blob.data(), off, hipMemcpyHostToDevice, load_stream));
   HIP_CHECK(hipStreamSynchronize(load_stream));   // `blob` is freed on return
+  if (cluster_values) build_cluster(*S);
   // the segment now references its chunk dictionaries' ids (released by ~Segment)
   S->engine = this;
   for (auto& c : S->cols)
@@ -549,6 +551,67 @@ std::shared_ptr<Segment> Engine::build_segment(const std::string& key, const uin
   return S;
 }
 
+// The name-clustered value copy (layout.hpp CluTile): per eligible tile -- lean_tile's conditions on the name and value
+// columns -- a block [cpref | cvals | crows], filled by clu_build on the load stream from the streams just uploaded.
+// The host loader, the staged bytes and the host link traffic are what they were; the descriptors are the only upload.
+// An allocation that fails leaves the segment without a copy (it serves every query on the other kernels) and is
+// counted (clu_alloc_failed).
+void Engine::build_cluster(Segment& S) {
+  const int cn = S.col_index(kName), cv = S.col_index(kValue);
+  const size_t nt = S.tiles.size();
+  if (cn < 0 || cv < 0 || nt == 0) return;
+  const HostCol& N = S.cols[size_t(cn)];
+  const HostCol& V = S.cols[size_t(cv)];
+  if (!N.is_string || V.is_string || N.tcols.size() != nt || V.tcols.size() != nt) return;
+  std::vector<CluTile> desc(nt, CluTile{CLU_NO_COPY, 0u, 0u});
+  size_t off = align_up(nt * sizeof(CluTile), CLU_BLOCK_ALIGN);
+  uint32_t copies = 0;
+  bool all_sorted = true;
+  int64_t widest = -1;
+  for (size_t t = 0; t < nt; t++) {
+    const TileCol& a = N.tcols[t];
+    const TileCol& b = V.tcols[t];
+    const TileDesc& td = S.tiles[t];
+    const bool ok = a.kind == PAGE_DICT && a.dict_n >= 1 && a.dict_n <= 64 && a.bw >= 1 && a.bw <= 6 && !a.has_nulls &&
+                    a.nruns >= 1 && a.nruns <= RUN_CAP && b.kind == PAGE_PLAIN64 && !b.has_nulls && td.nrows >= 1 &&
+                    td.nrows <= TILE_ROWS;
+    if (ok) {
+      desc[t] = CluTile{off, td.nrows, a.dict_n};
+      off += align_up(CLU_PREF_BYTES + size_t(td.nrows) * 10, CLU_BLOCK_ALIGN);
+      copies++;
+    }
+    if (!ok || !(td.pad & TILE_TS_SORTED) || td.ts_min > td.ts_max) all_sorted = false;
+    else widest = std::max(widest, td.ts_max - td.ts_min);
+  }
+  // The host hands scan_clu whole segments only (eval_plan.cpp), so a copy that does not cover every tile, or a segment
+  // with an unsorted tile, could serve no query: nothing is allocated, built or charged to the cache for it.
+  if (copies != nt || !all_sorted) return;
+  if (hipMalloc(&S.d_clu, off) != hipSuccess) {
+    (void)hipGetLastError();   // (the failed hipMalloc left HIP's thread-local last error set)
+    S.d_clu = nullptr;
+    clu_alloc_failed++;        // lk_engine_stats: loads that lost the copy to HBM pressure
+    return;
+  }
+  S.clu_bytes = off;
+  S.d_clu_desc = reinterpret_cast<const CluTile*>(S.d_clu);
+  HIP_CHECK(hipMemcpyAsync(S.d_clu, desc.data(), nt * sizeof(CluTile), hipMemcpyHostToDevice, load_stream));
+  CluBuild B{};
+  B.base = S.d_data;
+  B.name_tc = N.d_tcols;
+  B.val_tc = V.d_tcols;
+  B.name_runs = N.d_runs;
+  B.desc = S.d_clu_desc;
+  B.clu = S.d_clu;
+  B.ntiles = uint32_t(nt);
+  HIP_CHECK(launch_clu_build(B, load_stream));
+  HIP_CHECK(hipStreamSynchronize(load_stream));   // `desc` is freed on return
+  S.clu_name_col = cn;
+  S.clu_val_col = cv;
+  S.clu_tiles = copies;
+  S.clu_all_sorted = true;   // (checked above: every tile has a copy and sorted timestamps)
+  S.clu_widest = widest;
+}
+
 size_t Engine::evict_lru_locked(size_t target_bytes, const std::string& keep, std::vector<std::shared_ptr<Segment>>* out) {
   size_t freed = 0;
   while (cache_bytes > target_bytes) {
@@ -556,7 +619,7 @@ size_t Engine::evict_lru_locked(size_t target_bytes, const std::string& keep, st
     for (auto it = cache.begin(); it != cache.end(); ++it)
       if (it->first != keep && (victim == cache.end() || it->second->last_use < victim->second->last_use)) victim = it;
     if (victim == cache.end()) break;
-    const size_t b = victim->second->data_bytes + victim->second->meta_bytes;
+    const size_t b = victim->second->hbm_bytes();
     cache_bytes -= b;
     freed += b;
     evictions++;
@@ -614,10 +677,10 @@ int Engine::put_segment(const std::string& key, const uint8_t* data, size_t size
   load_ms_total += S->load_ms;
   auto it = cache.find(key);
   if (it != cache.end()) {
-    cache_bytes -= it->second->data_bytes + it->second->meta_bytes;
+    cache_bytes -= it->second->hbm_bytes();
     dead.push_back(std::move(it->second));
   }
-  cache_bytes += S->data_bytes + S->meta_bytes;
+  cache_bytes += S->hbm_bytes();
   cache[key] = S;
   if (hbm_budget) evict_lru_locked(hbm_budget, key, &dead);
   return LK_OK;

@@ -31,6 +31,20 @@ struct Segment : SegmentData {
   uint8_t* d_data = nullptr;                     // page streams (def levels / values), 16-B aligned
   void* d_meta = nullptr;
   size_t meta_bytes = 0;
+  // The name-clustered value copy (layout.hpp CluTile): one allocation [CluTile x tiles | per-tile blocks],
+  // built on the device at load from the `_cardinalhq.name` / `_cardinalhq.value` columns (clu_name_col / clu_val_col);
+  // null when the engine option is off, when some tile is not eligible or not TILE_TS_SORTED (scan_clu takes whole
+  // segments only, so a partial copy could serve no query) or when its allocation failed -- every query then takes the
+  // other kernels.  clu_all_sorted: every tile has a copy and TILE_TS_SORTED (true whenever d_clu is set);
+  // clu_widest: the widest tile's ts_max - ts_min (the host's whole-segment rule, clu.hpp clu_segment_taken).
+  uint8_t* d_clu = nullptr;
+  const CluTile* d_clu_desc = nullptr;
+  size_t clu_bytes = 0;
+  int clu_name_col = -1, clu_val_col = -1;
+  uint32_t clu_tiles = 0;
+  bool clu_all_sorted = false;
+  int64_t clu_widest = -1;
+  size_t hbm_bytes() const { return data_bytes + meta_bytes + clu_bytes; }   // the segment's cache weight
   bool from_put = false;                         // registered by lk_segment_put (its key is not a file path)
   std::atomic<uint64_t> last_use{0};             // LRU clock value of the last lookup (cache eviction)
   struct Engine* engine = nullptr;               // whose dictionaries its remaps reference (refs released at ~Segment)
@@ -156,6 +170,10 @@ struct Engine {
   // the least recently used segments, as the worker's weighted Caffeine cache does (WorkerApi.scala:53-64).  A
   // segment an evaluation still holds is freed when that evaluation drops it.
   size_t hbm_budget = 0;
+  // lk_engine_create {"cluster_values": false}: segments load without the name-clustered value copy (10 B per row of
+  // eligible tiles), for deployments that prefer the cache capacity to scan_clu
+  bool cluster_values = true;
+  std::atomic<size_t> clu_alloc_failed{0};       // loads whose copy allocation failed (the segment serves the old path)
   std::atomic<uint64_t> use_clock{0};
   size_t evictions = 0;
   // Keys registered with lk_segment_put that the LRU policy evicted since: an evaluation naming one fails with
@@ -226,6 +244,7 @@ struct Engine {
   ~Engine();
   GlobalDict& dict(const std::string& col);
   std::shared_ptr<Segment> build_segment(const std::string& key, const uint8_t* data, size_t size);
+  void build_cluster(Segment& S);                // caller holds dev_mu; S's host tile / column tables still present
   int put_segment(const std::string& key, const uint8_t* data, size_t size, bool from_put = true);
   std::shared_ptr<Segment> get_segment(const std::string& key, bool load_on_miss);
   std::unique_ptr<CallCtx> acquire_ctx();

@@ -140,6 +140,7 @@ struct DevState {
   bool fast_done = false;         // rows already written by the speculative finalize
   uint32_t fast_rows = 0;
   unsigned long long plan_bytes = 0;
+  uint32_t clu_tiles = 0;         // tiles scan_clu took (counted with the plan bytes: flags[1])
   uint32_t hflags = 0;
   int attempts = 0;
   // multi-GPU reduce
@@ -641,7 +642,19 @@ uint32_t run_scan(const EvalCall& C, const Plan& pl, DevState& dv) {
     HIP_TRY(hipMemsetAsync(dv.P.stamps, 0, nstamp * 8, dv.st));
   }
   dv.launch_ms = ms_since(C.t_start);   // host staging done, scan enqueued
-  if (pl.cs.ncells && !pl.sg.qsegs.empty()) HIP_TRY(launch_scan(dv.P, dv.kagg, dv.st));
+  if (pl.cs.ncells && !pl.sg.qsegs.empty()) {
+    // scan_clu's segments are the last n_clu of the staged descriptors (plan_cluster); the other fused kernels see the
+    // rest (none: not launched)
+    QParams Po = dv.P;
+    Po.nsegs -= pl.sg.n_clu;
+    HIP_TRY(launch_scan(Po, dv.kagg, dv.st));
+    if (pl.sg.n_clu) {
+      QParams Pc = dv.P;
+      Pc.segs += Po.nsegs;
+      Pc.nsegs = pl.sg.n_clu;
+      HIP_TRY(launch_scan_clu(Pc, dv.kagg, dv.st));
+    }
+  }
   if (pl.cs.ncells && !pl.sg.gsegs.empty()) {   // general row scan (numeric comparison leaves, union_by_name promotion)
     const XParams XG = general_scan_params(pl, dv, XMODE_AGG);
     HIP_TRY(XG.nnd ? launch_ex_scan_numdim(XG, dv.st) : launch_ex_scan(XG, dv.st));
@@ -665,6 +678,7 @@ uint32_t run_scan(const EvalCall& C, const Plan& pl, DevState& dv) {
       dv.fast_rows = tail[4];
       dv.fast_done = true;
       memcpy(&dv.plan_bytes, tail + 2, 8);
+      dv.clu_tiles = tail[1];
       return tail[0];
     }
   }
@@ -717,6 +731,7 @@ uint32_t run_scan(const EvalCall& C, const Plan& pl, DevState& dv) {
         expand_ts_runs(C.E, C.res->ts, Fs.bucket_pos[pl.cs.nbuckets], Fs);
         HIP_TRY(hipStreamSynchronize(dv.st));
         memcpy(&dv.plan_bytes, fl + 2, 8);
+        dv.clu_tiles = fl[1];
         return fl[0];
       }
     }
@@ -724,6 +739,7 @@ uint32_t run_scan(const EvalCall& C, const Plan& pl, DevState& dv) {
   HIP_TRY(hipMemcpyAsync(fl, dv.P.flags, 16, hipMemcpyDeviceToHost, dv.st));
   HIP_TRY(hipStreamSynchronize(dv.st));
   memcpy(&dv.plan_bytes, fl + 2, 8);
+  dv.clu_tiles = fl[1];
   return fl[0];
 }
 
@@ -778,7 +794,10 @@ void scan_agreed(const EvalCall& C, const Plan& pl, DevState& dv) {
     throw MetricsUnaligned{};
   }
   if ((dv.hflags & FLAG_MIN_NAN) && pl.qs.agg == AGG_MIN && pl.qs.merged && !pl.cs.min_max_nulls) throw MinNanApart{};
-  if (dv.hflags & FLAG_CELL_RANGE) throw PlanError(LK_ERR_DEVICE, "internal: bucket outside the table");
+  if (dv.hflags & FLAG_CELL_RANGE)   // (scan_clu raises the same flag for a tile of its segments that its rule does not take)
+    throw PlanError(LK_ERR_DEVICE, pl.sg.n_clu ? "internal: bucket outside the table, or a tile of a clustered segment outside scan_clu's "
+                                                 "rule (LK_NO_CLUSTER=1 evaluates without the clustered copy)"
+                                               : "internal: bucket outside the table");
   if (dv.hflags & FLAG_NUMDIM_MISS) throw PlanError(LK_ERR_DEVICE, "internal: a numeric groupBy value the discovery pass did not list");
   if (dv.hflags & FLAG_HASH_FULL) throw PlanError(LK_ERR_MEMORY, "aggregation hash table full at its bound");
   // DDSketch.accept on NaN / a magnitude beyond the mapping's range throws in the worker's stream stage: the
@@ -1260,6 +1279,8 @@ void write_stats(const EvalCall& C, const Plan& pl, const DevState& dv, const Co
   if (!pl.gp.bad_msg.empty()) C.res->stats += ",\"first_glob_error\":\"" + json_escape(pl.gp.bad_msg) + "\"";
   if (C.redo) C.res->stats += ",\"redo\":" + std::to_string(C.redo);   // 1: metrics at 1 ms, 2: MIN cells kept per glob
   if (dv.dense_shape) C.res->stats += ",\"lean_dense_shape\":1";
+  C.res->stats += std::string(",\"clustered\":") + (pl.sg.n_clu && pl.cs.ncells ? "1" : "0");   // scan_clu was launched
+  if (C.flags & LK_PLAN_BYTES) C.res->stats += ",\"clustered_tiles\":" + std::to_string(dv.clu_tiles);
   if (!pl.qs.numgbs.empty()) {
     std::string nd = ",\"numeric_dims\":[";
     for (size_t k = 0; k < pl.qs.numgbs.size(); k++)
@@ -1357,6 +1378,7 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   plan_segments(C, pl.qs, pl.fp, pl.gp, pl.cs, pl.sg);
   stage("qsegs");
   plan_table_mode(pl.qs, pl.sg, pl.cs);
+  plan_cluster(pl.cs, pl.sg);
   stage("truth");
 
   DevState dv;

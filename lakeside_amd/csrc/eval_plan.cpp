@@ -15,6 +15,7 @@
 #include <unordered_set>
 
 #include "../../include/lakeside_text.h"
+#include "clu.hpp"
 #include "comm.hpp"
 #include "hostutil.hpp"
 #include "layout.hpp"
@@ -814,6 +815,15 @@ void plan_segments(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp
   // row scan (ex_scan AGG mode): every segment of a numeric-leaf query, and segments whose timestamp or value column
   // needs union_by_name promotion (INT32 timestamps; INT32 / INT64 / FLOAT values, cast through FLOAT where the glob's
   // value type is FLOAT).  Both kinds aggregate into the same table.
+  // scan_clu's query shape (clu_kernel.hpp): one string column, the name, filtered through a truth table; SUM, MIN or
+  // MAX of `_cardinalhq.value` with no value leaf, sketch or cardinality estimate; buckets on the step grid.
+  // LK_NO_CLUSTER=1 (read per call: A/B) sends every segment down the other kernels, as do the switches that turn
+  // off the machinery it relies on.
+  const bool clu_query = fp.cols.size() == 1 && !qs.tagq && fp.cols[0].name == kName && !fp.truth.empty() &&
+                         (qs.agg == AGG_SUM || qs.agg == AGG_MIN || qs.agg == AGG_MAX) && !qs.sketch && !qs.ces &&
+                         !qs.numeric && !fp.vleaf && qs.nums.empty() && qs.numgbs.empty() && !qs.metrics && !qs.fchart &&
+                         !qs.no_value_col && qs.vcol == kValue && gp.step > 0 && !getenv("LK_NO_CLUSTER") &&
+                         !getenv("LK_NO_LEAN_SPLIT") && !getenv("LK_NO_SPLIT");
   try {
   for (size_t gi = 0; gi < gp.globs.size() && cs.nbuckets; gi++) {
     const GlobInfo& g = gp.globs[gi];
@@ -888,6 +898,14 @@ void plan_segments(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp
       // vleaf: only scan_lean tests the value leaves -- a segment it does not take whole goes to the general row scan
       if (fp.vleaf && (!seg_lean || !fp.vleaf_shape)) general = true;
       if (!general) sg.all_lean = sg.all_lean && seg_lean;
+      // scan_clu takes the segment whole: its copy was built from these two columns, covers every tile, and every
+      // tile that meets the window is pinned or split (clu.hpp) -- no other kernel then runs over the segment
+      if (clu_query && !general && seg_lean && S.d_clu && S.clu_name_col == S.col_index(kName) &&
+          S.clu_val_col == S.col_index(kValue) && !(q.cols[1].pad & (VCONV_VIA_FLOAT | VCONV_TEXT)) &&
+          clu_segment_taken(S.clu_all_sorted, S.clu_widest, gp.step)) {
+        q.clu = S.d_clu_desc;
+        q.clu_base = S.d_clu;
+      }
       q.tile_begin = sg.total_tiles;
       sg.seg_begin.push_back(sg.total_tiles);
       sg.total_tiles += q.ntiles;
@@ -932,6 +950,16 @@ void plan_table_mode(const QueryShape& qs, const SegPlan& sg, CellSpace& cs) {
   cs.cap = cs.hash_mode ? std::min<uint64_t>(cs.cap_max, std::max<uint64_t>(1 << 16, std::min<uint64_t>(pow2(2 * hash_bound), 1 << 25))) : 0;
   if (cs.hash_mode && getenv("LK_HASH_INIT_SLOTS"))   // tests only: a deliberately small first table (regrowth path)
     cs.cap = std::min<uint64_t>(cs.cap_max, pow2(std::max<uint64_t>(64, uint64_t(atoll(getenv("LK_HASH_INIT_SLOTS"))))));
+}
+
+void plan_cluster(const CellSpace& cs, SegPlan& sg) {
+  if (cs.hash_mode)   // scan_clu merges into dense tables only
+    for (auto& q : sg.qsegs) q.clu = nullptr, q.clu_base = nullptr;
+  sg.n_clu = 0;
+  if (std::none_of(sg.qsegs.begin(), sg.qsegs.end(), [](const QSeg& q) { return q.clu != nullptr; })) return;
+  // (stable: each kind keeps its order; QSeg::tile_begin is a statistic, no kernel indexes by it)
+  const auto mid = std::stable_partition(sg.qsegs.begin(), sg.qsegs.end(), [](const QSeg& q) { return q.clu == nullptr; });
+  sg.n_clu = uint32_t(sg.qsegs.end() - mid);
 }
 
 }  // namespace lk

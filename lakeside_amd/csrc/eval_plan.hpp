@@ -226,7 +226,10 @@ struct SegPlan {
   bool vals_integral = true;
   double vals_abs_max = 0.0, vals_rows = 0.0;
   bool all_lean = true;       // every fused-kernel tile is scan_lean's (the general kernel need not run)
-  int local_err = 0;          // distributed: a rank-local failure, agreed on with the other ranks after the scan
+  // scan_clu's segments (QSeg::clu set by plan_segments, kept by plan_cluster): the last n_clu of qsegs; the kernels
+  // before it see only qsegs[0 .. size - n_clu)
+  uint32_t n_clu = 0;
+  int local_err = 0;         // distributed: a rank-local failure, agreed on with the other ranks after the scan
   std::string local_msg;
 };
 
@@ -272,6 +275,9 @@ void plan_truth(const EvalCall& C, const QueryShape& qs, FilterPlan& fp);
 void plan_segments(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp, const GlobPlan& gp, const CellSpace& cs,
                    SegPlan& sg);
 void plan_table_mode(const QueryShape& qs, const SegPlan& sg, CellSpace& cs);
+// After the table mode is known: the segments scan_clu takes whole go to the end of qsegs (sg.n_clu of them); a
+// hash-mode table keeps every segment on the other kernels.
+void plan_cluster(const CellSpace& cs, SegPlan& sg);
 
 // The pure part of the filter planning (filter_plan.cpp: the request and the shape alone, no Engine, no HIP call):
 // shape_gate's leaf loop (all_leaves, nums, numeric), and what plan_filter / plan_truth do for a call.

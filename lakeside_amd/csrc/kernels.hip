@@ -780,6 +780,19 @@ hipError_t launch_scan(const QParams& P, int agg, hipStream_t stream) {
   return hipGetLastError();
 }
 
+hipError_t launch_scan_clu(const QParams& P, int agg, hipStream_t stream) {
+  if (P.max_tiles == 0 || P.nsegs == 0) return hipSuccess;
+  if (P.nstr != 1 || P.hkeys || !P.truth) return hipErrorInvalidValue;
+  const dim3 grid((P.max_tiles + BLOCK / 64 - 1) / (BLOCK / 64), P.nsegs);   // a wave per tile
+  switch (agg) {
+    case AGG_SUM: launch_clu<AGG_SUM>(P, grid, stream); break;
+    case AGG_MIN: launch_clu<AGG_MIN>(P, grid, stream); break;
+    case AGG_MAX: launch_clu<AGG_MAX>(P, grid, stream); break;
+    default: return hipErrorInvalidValue;   // no quiet fall-back: the host asks only for these
+  }
+  return hipGetLastError();
+}
+
 // finalize_scan on its own (the formula kernels' block and bucket counts, formula_kernels.hip)
 hipError_t launch_scan_counts(uint32_t* counts, uint32_t n, hipStream_t st) {
   hipLaunchKernelGGL(finalize_scan, dim3(1), dim3(1024), 0, st, counts, n);

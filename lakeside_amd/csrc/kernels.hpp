@@ -243,6 +243,20 @@ hipError_t launch_ex_gather(const GParams& G, hipStream_t stream);
 hipError_t launch_merge_tables(const TableRef& T, const unsigned long long* parts, int world, size_t nc, int agg,
                                hipStream_t stream);
 hipError_t launch_scan(const QParams& P, int agg, hipStream_t stream);
+// scan_clu (clu_kernel.hpp) over P.segs[0 .. nsegs): segments that carry the name-clustered value copy and whose every
+// tile it takes (QSeg::clu set); agg is AGG_SUM, AGG_MIN or AGG_MAX, the table dense
+hipError_t launch_scan_clu(const QParams& P, int agg, hipStream_t stream);
+// clu_build (clu_kernels.hip): the clustered copy of every tile of one segment whose descriptor has a block
+struct CluBuild {
+  const uint8_t* base;             // segment streams
+  const TileCol* name_tc;          // per tile: the name column, the value column
+  const TileCol* val_tc;
+  const RunDesc* name_runs;
+  const CluTile* desc;             // per tile (device copy)
+  uint8_t* clu;                    // the copy area
+  uint32_t ntiles;
+};
+hipError_t launch_clu_build(const CluBuild& B, hipStream_t stream);
 // lean tables: restore the rows / cnt fields the scan did not accumulate (LEAN_* in layout.hpp)
 hipError_t launch_remap_ids(uint32_t* p, unsigned long long n, const uint32_t* map, hipStream_t stream);
 hipError_t launch_fixup_table(const QParams& P, unsigned long long nc, int agg, hipStream_t stream);

@@ -87,6 +87,23 @@ struct TileCol {            // 64 B: everything the kernel needs about one colum
 };
 static_assert(sizeof(TileCol) == 64, "TileCol layout");
 
+// The name-clustered value copy (built at load by clu_build, read by scan_clu): per eligible tile -- the name column
+// PAGE_DICT with dict_n <= 64 and 1 <= bw <= 6, the value column PAGE_PLAIN64, no NULL in either over the tile -- a
+// block at `off` of the segment's copy area:
+//   cpref : CLU_PREF_BYTES: dict_n + 1 uint32 prefix counts over the chunk-dictionary codes (entries up to 64 repeat
+//           the total), so code c's elements are [cpref[c], cpref[c + 1])
+//   cvals : nrows raw 8-B value words grouped by code, codes ascending, rows ascending within a code
+//   crows : nrows uint16, each element's row within the tile
+// 10 B per row of eligible tiles.  A name filter's passing values are one contiguous range per (tile, code).
+struct CluTile {            // 16 B, one per tile of a segment that has a copy area
+  uint64_t off;             // byte offset of the tile's block in the copy area; CLU_NO_COPY: the tile has no copy
+  uint32_t nrows;
+  uint32_t dict_n;
+};
+constexpr uint64_t CLU_NO_COPY = ~0ull;
+constexpr uint32_t CLU_PREF_BYTES = 272;     // 65 prefix counts, padded so cvals stays 16-B aligned
+constexpr uint32_t CLU_BLOCK_ALIGN = 128;    // blocks start on an HBM line
+
 struct QCol {               // one query column in one segment
   const PageDesc* pages;
   const RunDesc* runs;
@@ -112,6 +129,10 @@ struct QSeg {
   int64_t win_lo;           // glob window [min startTs, max endTs) (Commons.scala:225-226)
   int64_t win_hi;
   QCol cols[MAXQCOL];
+  // the name-clustered value copy, set only in the segments scan_clu takes (query column 2 is the copy's name column,
+  // column 1 its value column; eval_plan.cpp plan_segments / plan_cluster); null otherwise
+  const CluTile* clu;
+  const uint8_t* clu_base;
 };
 
 enum Agg : int { AGG_SUM = 0, AGG_MIN = 1, AGG_MAX = 2, AGG_COUNT = 3 };

@@ -1,5 +1,5 @@
 // Instantiations of the fused scan kernels (scan_kernel.hpp, lean_kernel.hpp) and their host dispatch; included by the
-// scan_<agg>_<lean|tiles>_<d|h>.hip units and (dispatch only) by kernels.hip.
+// scan_<agg>_<lean|tiles|clu>_<d|h>.hip units and (dispatch only) by kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +7,9 @@
 #include "kernels.hpp"
 #if defined(LK_INST_LEAN) || defined(LK_INST_TILES)
 #include "scan_kernel.hpp"
+#endif
+#ifdef LK_INST_CLU
+#include "clu_kernel.hpp"
 #endif
 
 namespace lk {
@@ -18,6 +21,16 @@ template <int AGG, bool HASH>
 void launch_lean(const QParams& P, dim3 grid, hipStream_t st);    // lean tiles (lean_kernel.hpp), by late columns
 template <int AGG, bool HASH>
 void launch_tiles(const QParams& P, dim3 grid, hipStream_t st);   // every other tile (scan_kernel.hpp)
+
+template <int AGG>
+void launch_clu(const QParams& P, dim3 grid, hipStream_t st);     // the clustered copy's tiles (clu_kernel.hpp); dense only
+
+#ifdef LK_INST_CLU
+template <int AGG>
+void launch_clu(const QParams& P, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL((scan_clu<AGG>), grid, dim3(BLOCK), 0, st, P);
+}
+#endif
 
 #ifdef LK_INST_LEAN
 template <int AGG, bool HASH>
