@@ -24,7 +24,7 @@ HIP_OBJS  = $(OBJDIR)/kernels.o $(OBJDIR)/ex_kernels.o $(OBJDIR)/formula_kernels
 HDRS = $(wildcard $(SRC)/*.hpp) $(SRC)/unicode_tables.inc include/lakeside_gpu.h include/lakeside_regex.h include/lakeside_text.h
 # device code includes only these (host-only header edits do not rebuild the kernels); lean_kernel.hpp only the
 # scan_lean units, scan_kernel.hpp only the scan units
-DEV_HDRS = $(SRC)/device_common.hpp $(SRC)/kernels.hpp $(SRC)/layout.hpp $(SRC)/scan_inst.hpp $(SRC)/bucket.hpp $(SRC)/clu.hpp
+DEV_HDRS = $(SRC)/device_common.hpp $(SRC)/kernels.hpp $(SRC)/layout.hpp $(SRC)/scan_inst.hpp $(SRC)/bucket.hpp $(SRC)/clu.hpp $(SRC)/clu_reduce.hpp
 # the formula kernels: correctly rounded IEEE double, one operation at a time (no contraction; they use no atomics on
 # floating point, so -munsafe-fp-atomics selects nothing in this unit)
 $(OBJDIR)/formula_kernels.o: HIPFLAGS += -ffp-contract=off

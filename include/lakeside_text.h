@@ -59,6 +59,11 @@ void lk_clu_sim(const int64_t* ts_min, const int64_t* ts_max, const uint8_t* sor
                 int64_t win_hi, int64_t step, int64_t base, uint64_t nbuckets, int split_ok, uint8_t* kind, int64_t* b0,
                 uint32_t* nsb);
 int lk_clu_segment_taken(int all_copies_sorted, int64_t widest, int64_t step);
+/* The bytes of one tile block of the clustered copy (lakeside_amd/csrc/clu.hpp, clu_block_bytes: what the engine
+ * allocates and charges per tile) for a tile of nrows rows whose name chunk dictionary has dict_n entries (taken as
+ * 1 .. 64); the byte offsets within the block of the per-code aggregates, the values and the row indices go to
+ * agg_off / vals_off / rows_off where non-NULL. */
+uint64_t lk_clu_block_bytes(uint32_t nrows, uint32_t dict_n, uint32_t* agg_off, uint32_t* vals_off, uint64_t* rows_off);
 
 /* Plans the filter of a PushDownRequest as the evaluator does before it reads a segment (lakeside_amd/csrc/
  * filter_plan.cpp: the leaf loop of the shape gate, plan_filter, plan_truth); numeric_group_bys[0..n) are the groupBys

@@ -10,10 +10,22 @@
 #include <stdint.h>
 
 #include "bucket.hpp"
+#include "layout.hpp"
 
 namespace lk {
 
 constexpr uint32_t CLU_SPLIT_MAX = 4;   // class boundaries of a split tile at most (scan_lean's LEAN_SPLIT_MAX)
+
+// A tile block's layout (layout.hpp, CluTile), stated once for Engine::build_cluster, clu_build and scan_clu and pinned
+// on the CPU (tests/test_clu_layout_cpu.py through clu_sim.cpp): [cpref + NaN mask | cagg | cvals | crows].
+// dict_n is taken as 1 .. 64, as the builder takes it.
+LK_BK_HD inline uint32_t clu_dict_n(uint32_t dict_n) { return dict_n < 1u ? 1u : (dict_n > 64u ? 64u : dict_n); }
+LK_BK_HD inline uint32_t clu_vals_off(uint32_t dict_n) { return CLU_AGG_OFF + clu_dict_n(dict_n) * uint32_t(sizeof(CluAgg)); }
+LK_BK_HD inline uint64_t clu_rows_off(uint32_t nrows, uint32_t dict_n) { return clu_vals_off(dict_n) + uint64_t(nrows) * 8u; }
+LK_BK_HD inline uint64_t clu_block_bytes(uint32_t nrows, uint32_t dict_n) {
+  const uint64_t b = clu_rows_off(nrows, dict_n) + uint64_t(nrows) * 2u;
+  return (b + (CLU_BLOCK_ALIGN - 1u)) / CLU_BLOCK_ALIGN * CLU_BLOCK_ALIGN;
+}
 
 enum CluKind : uint32_t {
   CLU_NONE = 0,     // outside the glob window: no row of the tile counts

@@ -4,23 +4,29 @@
 // neither scan_lean nor scan_tiles runs over them.
 //
 // Per tile: the passing-code mask exactly as scan_lean computes it (remap -> strtab -> T / F bits -> truth word,
-// leaf_false included), then for each passing code c the contiguous range cvals[cpref[c] .. cpref[c + 1]) streamed
-// with coalesced 8-B loads.  A pinned tile's elements all land in one bucket; a split tile also streams crows (the
-// element's row within the tile) and takes each element's class from its row index against boundary rows found with
-// scan_lean's two-round timestamp search (256 samples, then the sample gap holding each boundary).  No run staging,
-// no chunk table, no row list, no LDS: the wave reduces per (code, class) and lane 0 merges once per (tile, code,
-// class) through global_merge, which honours the LEAN_* flags, the -0.0 empty marker, exact_sum and FLAG_MIN_NAN.
+// leaf_false included).  A pinned tile's elements all land in one bucket, and what its passing codes contribute --
+// each code's (hi, lo, count) or extreme -- was fixed when the segment was loaded: lane c merges the tile's stored
+// aggregate cagg[c] (built by clu_build with clu_reduce_pinned, clu_reduce.hpp) through global_merge itself and the
+// tile moves no value.  A split tile streams, for each passing code c, the contiguous range cvals[cpref[c] ..
+// cpref[c + 1]) with coalesced 8-B loads and crows (the element's row within the tile), and takes each element's class
+// from its row index against boundary rows found with scan_lean's two-round timestamp search (256 samples, then the
+// sample gap holding each boundary): the wave reduces per (code, class) and lane 0 merges once per (tile, code, class).
+// No run staging, no chunk table, no row list, no LDS.  global_merge honours the LEAN_* flags, the -0.0 empty marker,
+// exact_sum and FLAG_MIN_NAN.  LK_NO_CLU_AGG=1 (SPLIT_OK_NO_CLU_AGG) streams pinned tiles too, with clu_reduce_pinned
+// (one merge per (tile, code)): the same rows bit for bit, the A/B and the tests' proof of which path ran.
 //
-// Shape: one wave per tile, four tiles per 256-thread workgroup, no barrier.  C2's tile has about 4,096 passing values
-// (32 KB): a wave holds 16 loads per lane (8 KB) in flight, and 16 waves per CU keep 128 KB per CU in flight -- the
-// stream is latency-bound, so what counts is bytes in flight per CU, and a wave per tile needs no cross-wave reduction
-// (one merge per (tile, code, class) as it stands).  Measured in this shape: C2's scan 1.114 -> 0.163 ms,
-// c2s10 1.206 -> 0.250 ms, dense (all 16 codes pass) 2.434 -> 1.733 ms.  A workgroup per tile and several tiles per
-// wave were not measured (DESIGN §9 lists the comparison as open).
+// Shape: one wave per tile, four tiles per 256-thread workgroup, no barrier.  A pinned tile is a chain of dependent
+// loads (QSeg -> TileDesc / CluTile / TileCol -> remap, cpref, cagg -> strtab -> truth word) and a few atomics; at a
+// 1 m step three of C2's four tiles are pinned.  A split tile of C2 has about 4,096 passing values (32 KB): a wave
+// holds 8 loads per lane of values and of rows in flight; the stream is latency-bound, so what counts is bytes in flight
+// per CU, and a wave per tile needs no cross-wave reduction.  Measured: C2's scan 0.159 -> 0.101 ms in the
+// kernel trace with the aggregates (1.114 ms before the copy), plan bytes 0.585 -> 0.165 GB.  A workgroup per tile and
+// several tiles per wave were not measured (DESIGN §9 lists the comparison as open).
 #pragma once
 #include <type_traits>
 
 #include "clu.hpp"
+#include "clu_reduce.hpp"
 #include "device_common.hpp"
 
 namespace lk {
@@ -48,6 +54,25 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
   const uint32_t dict_n = tc2->dict_n < 64u ? tc2->dict_n : 64u;
   const bool count_plan = P.plan_bytes != nullptr;
   uint64_t pbytes = 0;
+  const uint8_t* blk = Sp->clu_base + d.off;
+  // a pinned tile merges the copy's per-code aggregates (LK_NO_CLU_AGG=1: it streams the ranges, as a split tile must)
+  const bool use_agg = cc.kind == CLU_PINNED && !(P.split_ok & SPLIT_OK_NO_CLU_AGG) && d.nrows <= tdp->nrows;   // uniform
+
+  // lane c: the code's range [cs, ce) of cvals / crows and, for a pinned tile, its aggregate.  Loaded for every code
+  // beside the remap entry, before the truth word says which codes pass: the three depend on CluTile / TileCol alone,
+  // so the tile's chain of dependent round trips is no longer for them.
+  uint32_t cs, ce;
+  CluAgg ag = CluAgg{0.0, 0.0, 0ull, 0ull};
+  unsigned long long nanw = 0ull;
+  {
+    const uint32_t* cp = reinterpret_cast<const uint32_t*>(blk);
+    cs = cp[lane];
+    ce = cp[lane + 1u];
+    if (use_agg) {
+      if (lane < clu_dict_n(d.dict_n)) ag = reinterpret_cast<const CluAgg*>(blk + CLU_AGG_OFF)[lane];
+      if (AGG == AGG_MIN) nanw = *reinterpret_cast<const unsigned long long*>(blk + CLU_NAN_OFF);
+    }
+  }
 
   // passing codes: one ballot over the chunk dictionary (Kleene: the leaves' T/F bits of the code), as scan_lean
   uint32_t lut = 0;
@@ -74,18 +99,30 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
     return;
   }
 
-  const uint8_t* blk = Sp->clu_base + d.off;
-  uint32_t cs, ce;   // lane c: the code's range [cs, ce) of cvals / crows
-  {
-    const uint32_t* cp = reinterpret_cast<const uint32_t*>(blk);
-    cs = cp[lane];
-    ce = cp[lane + 1u];
-    ce = ce < nrows ? ce : nrows;
-    cs = cs < ce ? cs : ce;
-    if (count_plan && lane == 0) pbytes += uint64_t(dict_n + 1u) * 4u;
+  ce = ce < nrows ? ce : nrows;
+  cs = cs < ce ? cs : ce;
+  if (count_plan && lane == 0) pbytes += uint64_t(dict_n + 1u) * 4u;
+  const uint32_t stride = P.strp[0].dim_stride;
+  const unsigned long long glob_base = (unsigned long long)Sp->glob_slot * P.nbuckets;
+
+  if (use_agg) {   // uniform: every passing lane merges its own code (codes sharing a dim meet in the atomics)
+    if (pass && cs < ce) {
+      const unsigned long long cell = (glob_base + (unsigned long long)cc.b0) * P.ngroups + (lut & DIM_MASK) * stride;
+      global_merge<AGG, false>(P, cell, ce - cs, ce - cs, ag.hi, ag.lo, AGG == AGG_MIN ? ag.omin : ag.omax);
+    }
+    if (AGG == AGG_MIN && (nanw & emask) && lane == 0) atomicOr(P.flags, FLAG_MIN_NAN);
+    const unsigned long long mmask = count_plan ? __ballot(pass && cs < ce) : 0ull;
+    if (count_plan && lane == 0) {   // the 128-B lines of the merged entries (the NaN mask lies in cpref's)
+      unsigned long long lines = 0ull;
+      for (unsigned long long m = mmask; m; m &= m - 1ull)
+        lines |= 1ull << ((CLU_AGG_OFF + uint32_t(__builtin_ctzll(m)) * uint32_t(sizeof(CluAgg))) >> 7);
+      pbytes += 128u * uint64_t(__popcll(lines));
+      atomicAdd(P.plan_bytes, (unsigned long long)pbytes);
+    }
+    return;
   }
-  const __amdgpu_buffer_rsrc_t rv = make_rsrc(blk + CLU_PREF_BYTES, nrows * 8u);
-  const uint16_t* crows = reinterpret_cast<const uint16_t*>(blk + CLU_PREF_BYTES + size_t(nrows) * 8u);
+  const __amdgpu_buffer_rsrc_t rv = make_rsrc(blk + clu_vals_off(d.dict_n), nrows * 8u);
+  const uint16_t* crows = reinterpret_cast<const uint16_t*>(blk + clu_rows_off(nrows, d.dict_n));
 
   // split tiles: boundary rows (scan_lean's search, per wave: four samples / gap rows per lane)
   const bool split = cc.kind == CLU_SPLIT;
@@ -151,12 +188,10 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
     return c;
   };
 
-  const uint32_t stride = P.strp[0].dim_stride;
-  const unsigned long long glob_base = (unsigned long long)Sp->glob_slot * P.nbuckets;
   bool nan_seen = false;
 
-  // One passing code's range [s, s + n): NK classes (pinned: 1, every element in bucket b0; split: the in-window
-  // classes 1 .. nsb - 1, at most CLU_SPLIT_MAX - 1), U loads per lane in flight
+  // One passing code's range [s, s + n) of a split tile: NK classes (the in-window classes 1 .. nsb - 1, at most
+  // CLU_SPLIT_MAX - 1), U loads per lane in flight.  (A pinned tile's range: clu_reduce_pinned, below.)
   auto stream = [&](auto nkc, auto uc, uint32_t s, uint32_t n, uint32_t dim) __attribute__((always_inline)) {
     constexpr uint32_t NK = decltype(nkc)::value;
     constexpr uint32_t U = decltype(uc)::value;
@@ -246,7 +281,15 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
     if (s >= e) continue;   // the name is absent from the tile
     const uint32_t dim = (uni(__shfl(lut, int(c), 64)) & DIM_MASK) * stride;
     if (split) stream(std::integral_constant<uint32_t, CLU_SPLIT_MAX - 1u>{}, std::integral_constant<uint32_t, 8u>{}, s, e - s, dim);
-    else stream(std::integral_constant<uint32_t, 1u>{}, std::integral_constant<uint32_t, 16u>{}, s, e - s, dim);
+    else {   // pinned, streamed (LK_NO_CLU_AGG): the reduction the copy's aggregates were built with
+      const CluRed r = clu_reduce_pinned<AGG == AGG_SUM, AGG == AGG_MIN, AGG == AGG_MAX, 16u>(rv, s, e - s, lane, P.exact_sum != 0u);
+      nan_seen = nan_seen || r.nan;
+      if (lane == 0 && r.cnt) {
+        const unsigned long long cell = (glob_base + (unsigned long long)cc.b0) * P.ngroups + dim;
+        global_merge<AGG, false>(P, cell, r.cnt, r.cnt, r.hi, r.lo, AGG == AGG_MIN ? r.omin : r.omax);
+      }
+      if (count_plan && lane == 0) pbytes += 128u * uint64_t(((e * 8u + 127u) >> 7) - ((s * 8u) >> 7));
+    }
   }
   if (AGG == AGG_MIN && __ballot(nan_seen) && lane == 0) atomicOr(P.flags, FLAG_MIN_NAN);
   if (pbytes) atomicAdd(P.plan_bytes, (unsigned long long)pbytes);

@@ -3,9 +3,13 @@
 // stable counting sort of the tile's rows by chunk-dictionary code -- codes ascending, rows ascending within a code, so
 // the layout is deterministic.  Not a hot kernel: every row's code is decoded twice (histogram, then placement), and a
 // 256-row step ranks its rows by ballot within the wave and through per-wave counts in LDS across waves.
+// Then the per-code aggregates (`cagg`, the NaN mask): a wave takes codes w, w + 4, ... and reduces each one's range
+// of the cvals the workgroup has just written with clu_reduce_pinned (clu_reduce.hpp) -- the function scan_clu streams
+// a pinned tile's range with, so the stored triple is what that stream hands global_merge, bit for bit.
 // Every global store is clamped to the tile's block, every stream read goes through a buffer resource.
 #include <hip/hip_runtime.h>
 
+#include "clu_reduce.hpp"
 #include "device_common.hpp"
 #include "kernels.hpp"
 
@@ -17,6 +21,8 @@ __global__ __launch_bounds__(BLOCK) void clu_build(CluBuild B) {
   __shared__ LRun runs[RUN_CAP];
   __shared__ uint32_t next[64];        // histogram, then the next output position of every code
   __shared__ uint32_t wcnt[NW][64];    // the step's rows per (wave, code)
+  __shared__ uint32_t cst[65];         // cpref (the aggregate pass reads the ranges from here)
+  __shared__ unsigned long long nanm;  // bit c: a NaN among code c's values
   const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
   const uint32_t t = blockIdx.x;
   if (t >= B.ntiles) return;
@@ -33,14 +39,15 @@ __global__ __launch_bounds__(BLOCK) void clu_build(CluBuild B) {
   const __amdgpu_buffer_rsrc_t rvv = make_rsrc(B.base + tv->vals, tv->vals_len);
   uint8_t* blk = B.clu + d.off;
   uint32_t* cpref = reinterpret_cast<uint32_t*>(blk);
-  unsigned long long* cvals = reinterpret_cast<unsigned long long*>(blk + CLU_PREF_BYTES);
-  uint16_t* crows = reinterpret_cast<uint16_t*>(blk + CLU_PREF_BYTES + size_t(nrows) * 8u);
+  unsigned long long* cvals = reinterpret_cast<unsigned long long*>(blk + clu_vals_off(dict_n));
+  uint16_t* crows = reinterpret_cast<uint16_t*>(blk + clu_rows_off(nrows, dict_n));
 
   for (uint32_t i = tid; i < nr; i += BLOCK) {
     const RunDesc r = B.name_runs[tn->run_lo + i];
     runs[i] = LRun{r.start, r.off_lit, r.value};
   }
   if (tid < 64u) next[tid] = 0u;
+  if (tid == 0u) nanm = 0ull;
   for (uint32_t i = tid; i < NW * 64u; i += BLOCK) (&wcnt[0][0])[i] = 0u;
   __syncthreads();
   if (nr == 0u) return;                // uniform (an eligible tile has runs)
@@ -63,7 +70,8 @@ __global__ __launch_bounds__(BLOCK) void clu_build(CluBuild B) {
     }
     next[lane] = inc - n;
     cpref[lane] = inc - n;
-    if (lane == 63u) cpref[64] = inc;
+    cst[lane] = inc - n;
+    if (lane == 63u) cpref[64] = cst[64] = inc;
   }
   __syncthreads();
 
@@ -106,6 +114,26 @@ __global__ __launch_bounds__(BLOCK) void clu_build(CluBuild B) {
     }
     __syncthreads();
   }
+
+  // pass 3: cagg.  The cvals were stored by other lanes: each thread's stores are fenced before the barrier, and the
+  // reading waves fence again behind it before their buffer loads.
+  __threadfence();
+  __syncthreads();
+  __threadfence();
+  const __amdgpu_buffer_rsrc_t rcv = make_rsrc(reinterpret_cast<const uint8_t*>(cvals), nrows * 8u);
+  CluAgg* cagg = reinterpret_cast<CluAgg*>(blk + CLU_AGG_OFF);
+  for (uint32_t c = w; c < dict_n; c += NW) {   // uniform per wave
+    uint32_t ce = cst[c + 1u], cs = cst[c];     // clamped as scan_clu clamps cpref
+    ce = ce < nrows ? ce : nrows;
+    cs = cs < ce ? cs : ce;
+    const CluRed r = clu_reduce_pinned<true, true, true, 16u>(rcv, uni(cs), uni(ce - cs), lane, false);
+    if (lane == 0u) {
+      cagg[c] = CluAgg{r.hi, r.lo, r.omin, r.omax};
+      if (r.nan) atomicOr(&nanm, 1ull << c);
+    }
+  }
+  __syncthreads();
+  if (tid == 0u) *reinterpret_cast<unsigned long long*>(blk + CLU_NAN_OFF) = nanm;
 }
 
 }  // namespace

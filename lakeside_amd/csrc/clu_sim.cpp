@@ -15,6 +15,14 @@ extern "C" void lk_clu_sim(const int64_t* ts_min, const int64_t* ts_max, const u
   }
 }
 
+extern "C" uint64_t lk_clu_block_bytes(uint32_t nrows, uint32_t dict_n, uint32_t* agg_off, uint32_t* vals_off,
+                                       uint64_t* rows_off) {
+  if (agg_off) *agg_off = lk::CLU_AGG_OFF;
+  if (vals_off) *vals_off = lk::clu_vals_off(dict_n);
+  if (rows_off) *rows_off = lk::clu_rows_off(nrows, dict_n);
+  return lk::clu_block_bytes(nrows, dict_n);
+}
+
 extern "C" int lk_clu_segment_taken(int all_copies_sorted, int64_t widest, int64_t step) {
   return lk::clu_segment_taken(all_copies_sorted != 0, widest, step) ? 1 : 0;
 }

@@ -31,6 +31,7 @@
 #include "engine.hpp"
 #include "hll.hpp"
 #include "loader.hpp"
+#include "clu.hpp"
 #include "kernels.hpp"
 #include "layout.hpp"
 #include "codec.hpp"
@@ -552,8 +553,8 @@ std::shared_ptr<Segment> Engine::build_segment(const std::string& key, const uin
 }
 
 // The name-clustered value copy (layout.hpp CluTile): per eligible tile -- lean_tile's conditions on the name and value
-// columns -- a block [cpref | cvals | crows], filled by clu_build on the load stream from the streams just uploaded.
-// The host loader, the staged bytes and the host link traffic are what they were; the descriptors are the only upload.
+// columns -- a block [cpref | cagg | cvals | crows] (clu.hpp, clu_block_bytes), filled by clu_build on the load stream
+// from the streams just uploaded (cagg: every code's values reduced once, for scan_clu's pinned tiles).  The host loader, the staged bytes and the host link traffic are what they were; the descriptors are the only upload.
 // An allocation that fails leaves the segment without a copy (it serves every query on the other kernels) and is
 // counted (clu_alloc_failed).
 void Engine::build_cluster(Segment& S) {
@@ -577,7 +578,7 @@ void Engine::build_cluster(Segment& S) {
                     td.nrows <= TILE_ROWS;
     if (ok) {
       desc[t] = CluTile{off, td.nrows, a.dict_n};
-      off += align_up(CLU_PREF_BYTES + size_t(td.nrows) * 10, CLU_BLOCK_ALIGN);
+      off += size_t(clu_block_bytes(td.nrows, a.dict_n));
       copies++;
     }
     if (!ok || !(td.pad & TILE_TS_SORTED) || td.ts_min > td.ts_max) all_sorted = false;

@@ -351,6 +351,8 @@ void setup_scan(const EvalCall& C, const Plan& pl, DevState& dv) {
   // a group space far beyond scan_lean's LDS hash table (1M+ cells): register cells go straight to the global table
   dv.P.global_cells = (uint64_t(pl.dp.ngroups) * pl.cs.nbuckets >= (1ull << 20) && !getenv("LK_LDS_CELLS")) ? 1u : 0u;
   dv.P.split_ok = getenv("LK_NO_SPLIT") ? 0u : 1u;   // env: A/B only
+  // LK_NO_CLU_AGG=1 (read per call: A/B and the tests' proof of the path): scan_clu streams its pinned tiles
+  if (dv.P.split_ok && getenv("LK_NO_CLU_AGG")) dv.P.split_ok |= SPLIT_OK_NO_CLU_AGG;
   if (pl.fp.vleaf && !pl.sg.qsegs.empty()) {   // scan_lean tests the value leaves of every row its string conjuncts pass
     dv.P.nvl = uint32_t(pl.fp.nleaves.size());
     dv.P.vtab = pl.fp.vtab;

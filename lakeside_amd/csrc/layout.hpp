@@ -91,17 +91,30 @@ static_assert(sizeof(TileCol) == 64, "TileCol layout");
 // PAGE_DICT with dict_n <= 64 and 1 <= bw <= 6, the value column PAGE_PLAIN64, no NULL in either over the tile -- a
 // block at `off` of the segment's copy area:
 //   cpref : CLU_PREF_BYTES: dict_n + 1 uint32 prefix counts over the chunk-dictionary codes (entries up to 64 repeat
-//           the total), so code c's elements are [cpref[c], cpref[c + 1])
-//   cvals : nrows raw 8-B value words grouped by code, codes ascending, rows ascending within a code
+//           the total), so code c's elements are [cpref[c], cpref[c + 1]); at CLU_NAN_OFF, in the padding behind the
+//           65 counts, one 64-bit mask: bit c = a NaN among code c's values
+//   cagg  : at CLU_AGG_OFF, dict_n CluAgg entries: code c's values reduced as scan_clu reduces the range when it
+//           streams it for a pinned tile (clu_reduce.hpp, one function for both), so a pinned tile merges them instead;
+//           code c's count is cpref[c + 1] - cpref[c]
+//   cvals : at clu_vals_off(dict_n) (clu.hpp), nrows raw 8-B value words grouped by code, codes ascending, rows
+//           ascending within a code
 //   crows : nrows uint16, each element's row within the tile
-// 10 B per row of eligible tiles.  A name filter's passing values are one contiguous range per (tile, code).
+// 10 B per row of eligible tiles and 32 B per (tile, code).  A name filter's passing values are one contiguous range per
+// (tile, code).
 struct CluTile {            // 16 B, one per tile of a segment that has a copy area
   uint64_t off;             // byte offset of the tile's block in the copy area; CLU_NO_COPY: the tile has no copy
   uint32_t nrows;
   uint32_t dict_n;
 };
+struct CluAgg {             // 32 B: one code's values of one tile
+  double hi, lo;            // the compensated sum (exact_sum queries read hi alone: the same double either way)
+  uint64_t omin, omax;      // dbl_order extremes
+};
+static_assert(sizeof(CluAgg) == 32, "CluAgg layout");
 constexpr uint64_t CLU_NO_COPY = ~0ull;
-constexpr uint32_t CLU_PREF_BYTES = 272;     // 65 prefix counts, padded so cvals stays 16-B aligned
+constexpr uint32_t CLU_PREF_BYTES = 272;     // 65 prefix counts and the NaN mask
+constexpr uint32_t CLU_NAN_OFF = 264;        // the 8-B-aligned padding behind the counts
+constexpr uint32_t CLU_AGG_OFF = 288;        // 32-B aligned: an entry never straddles a 128-B line
 constexpr uint32_t CLU_BLOCK_ALIGN = 128;    // blocks start on an HBM line
 
 struct QCol {               // one query column in one segment
@@ -224,7 +237,9 @@ struct QParams {
   uint32_t exact_sum;
   // group spaces far beyond the tile's LDS hash table (C5's 10M container ids): cells go straight to the global table
   uint32_t global_cells;
-  // scan_lean split tiles (TILE_TS_SORTED tiles spanning a few buckets: rows bucketed by index, no timestamp gather)
+  // scan_lean split tiles (TILE_TS_SORTED tiles spanning a few buckets: rows bucketed by index, no timestamp gather):
+  // 0 off, else on.  Bit 1 (SPLIT_OK_NO_CLU_AGG; env LK_NO_CLU_AGG, A/B and tests): scan_clu streams its pinned tiles'
+  // value ranges instead of merging the copy's aggregates
   uint32_t split_ok;
   // Numeric comparison leaves on the value column (`value > 1.5`, BaseExpr.scala:488-498) in the fused kernel: a row
   // whose string conjuncts pass is kept iff vtab bit (its leaves' outcomes, bit k = leaf k) is set -- the numeric
@@ -233,6 +248,7 @@ struct QParams {
   uint32_t vtab;
   VLeaf vl[VLEAF_MAX];
 };
+constexpr uint32_t SPLIT_OK_NO_CLU_AGG = 2u;   // QParams::split_ok bit 1
 // scan_lean's direct table: LDS words by late-column count NL (the hash table's 8 KB for NL >= 1, so the kernels keep
 // their occupancy), at most LEAN_DIR_MAXSPAN buckets
 constexpr uint32_t LEAN_DIR_WORDS0 = 1536;
