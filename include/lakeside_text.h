@@ -64,6 +64,17 @@ int lk_clu_segment_taken(int all_copies_sorted, int64_t widest, int64_t step);
  * 1 .. 64); the byte offsets within the block of the per-code aggregates, the values and the row indices go to
  * agg_off / vals_off / rows_off where non-NULL. */
 uint64_t lk_clu_block_bytes(uint32_t nrows, uint32_t dict_n, uint32_t* agg_off, uint32_t* vals_off, uint64_t* rows_off);
+/* The bytes of one tile's sub-block area (clu.hpp, clu_sub_bytes: a tile's stride when dict_n is its segment's largest)
+ * for a tile of nrows rows (the area is sized for the most sub-blocks a tile can have, so nrows decides *nsub alone);
+ * where non-NULL: nsub = the tile's sub-blocks, sub_rows / sub_max = the constants, sagg_off = the byte offset of code
+ * c's aggregate of sub-block j (c, j as given), csub_off / nan_off = the offsets of the first code's csub entries and of
+ * the first code's NaN mask. */
+uint32_t lk_clu_sub_bytes(uint32_t nrows, uint32_t dict_n, uint32_t c, uint32_t j, uint32_t* nsub, uint32_t* sub_rows,
+                          uint32_t* sub_max, uint32_t* sagg_off, uint32_t* csub_off, uint32_t* nan_off);
+/* The whole-or-straddling rule of a split tile's sub-blocks (clu.hpp, clu_sub_class as scan_clu calls it): for a tile of
+ * nrows rows with boundary rows sb[0 .. nsb) (ascending; sb[k] = the first row of class k + 1; nsb <= 4), cls[j] = the
+ * class of every row of sub-block j, or 0xffffffff when the sub-block's rows must be streamed.  Returns the sub-blocks. */
+uint32_t lk_clu_sub_sim(uint32_t nrows, const uint32_t* sb, uint32_t nsb, uint32_t* cls);
 
 /* Plans the filter of a PushDownRequest as the evaluator does before it reads a segment (lakeside_amd/csrc/
  * filter_plan.cpp: the leaf loop of the shape gate, plan_filter, plan_truth); numeric_group_bys[0..n) are the groupBys

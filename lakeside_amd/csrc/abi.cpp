@@ -136,9 +136,9 @@ const char* lk_engine_stats(lk_engine* e) {
     o += "\"segments\":" + std::to_string(E.cache.size()) + ",\"segment_bytes\":" + std::to_string(E.cache_bytes) +
          ",\"evictions\":" + std::to_string(E.evictions) + ",\"load_ms\":" + std::to_string(E.load_ms_total) +
          ",\"load_host_ms\":" + std::to_string(E.load_host_ms_total);
-    size_t clu = 0;   // the clustered value copies' share of segment_bytes
-    for (auto& kv : E.cache) clu += kv.second->clu_bytes;
-    o += ",\"clu_bytes\":" + std::to_string(clu) + ",\"clu_alloc_failed\":" + std::to_string(E.clu_alloc_failed.load());
+    size_t clu = 0, sub = 0;   // the clustered value copies' and their sub-block areas' shares of segment_bytes
+    for (auto& kv : E.cache) clu += kv.second->clu_bytes, sub += kv.second->clu_sub_bytes;
+    o += ",\"clu_bytes\":" + std::to_string(clu) + ",\"clu_sub_bytes\":" + std::to_string(sub) + ",\"clu_alloc_failed\":" + std::to_string(E.clu_alloc_failed.load());
   }
   o += ",\"dict_compactions\":" + std::to_string(E.compactions) + ",\"dictionaries\":{";
   {

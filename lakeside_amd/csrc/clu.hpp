@@ -27,6 +27,43 @@ LK_BK_HD inline uint64_t clu_block_bytes(uint32_t nrows, uint32_t dict_n) {
   return (b + (CLU_BLOCK_ALIGN - 1u)) / CLU_BLOCK_ALIGN * CLU_BLOCK_ALIGN;
 }
 
+// A tile's sub-block area (a second area per segment, beside the blocks: nothing inside a block moves).  The tile is
+// cut into sub-blocks of CLU_SUB_ROWS rows; per chunk-dictionary code c (indexed like cagg):
+//   sagg : at 0, CLU_SUB_MAX CluAgg per code: code c's elements of sub-block j reduced with clu_reduce_pinned
+//          (32-B entries from a 128-B-aligned start: none straddles a 128-B line)
+//   csub : at clu_sub_csub_off, CLU_SUB_MAX + 1 uint32 per code: the element index, within the tile, of code c's first
+//          element whose row is >= CLU_SUB_ROWS * j (entries past the tile's sub-blocks repeat cpref[c + 1])
+//   snan : at clu_sub_nan_off, one uint16 per code: bit j = a NaN among code c's elements of sub-block j
+// A segment's tiles lie at a fixed stride, clu_sub_bytes of the segment's largest dict_n; a tile's offsets use its own.
+constexpr uint32_t CLU_SUB_ROWS = 4096;
+constexpr uint32_t CLU_SUB_MAX = TILE_ROWS / CLU_SUB_ROWS;   // 16
+constexpr uint32_t CLU_SUB_STRADDLE = ~0u;
+LK_BK_HD inline uint32_t clu_nsub(uint32_t nrows) { return (nrows + CLU_SUB_ROWS - 1u) / CLU_SUB_ROWS; }
+LK_BK_HD inline uint32_t clu_sub_sagg_off(uint32_t c, uint32_t j) { return (c * CLU_SUB_MAX + j) * uint32_t(sizeof(CluAgg)); }
+LK_BK_HD inline uint32_t clu_sub_csub_off(uint32_t dict_n) { return clu_dict_n(dict_n) * CLU_SUB_MAX * uint32_t(sizeof(CluAgg)); }
+LK_BK_HD inline uint32_t clu_sub_nan_off(uint32_t dict_n) { return clu_sub_csub_off(dict_n) + clu_dict_n(dict_n) * (CLU_SUB_MAX + 1u) * 4u; }
+LK_BK_HD inline uint32_t clu_sub_bytes(uint32_t dict_n) {
+  const uint32_t b = clu_sub_nan_off(dict_n) + clu_dict_n(dict_n) * 2u;
+  return (b + (CLU_BLOCK_ALIGN - 1u)) / CLU_BLOCK_ALIGN * CLU_BLOCK_ALIGN;
+}
+
+// Sub-block j of a split tile of nrows rows, rows [lo, hi) = [CLU_SUB_ROWS * j, min(CLU_SUB_ROWS * (j + 1), nrows)),
+// against the tile's boundary rows sb[0 .. nsb) (ascending; sb[k] is the first row of class k + 1): the sub-block is
+// whole when no boundary lies strictly inside (lo, hi) -- one exactly on its first row leaves it whole -- and then
+// every row has the class returned, the number of boundaries at or below lo.  CLU_SUB_STRADDLE: its rows' classes
+// differ, so its elements are streamed.
+LK_BK_HD inline uint32_t clu_sub_class(uint32_t j, uint32_t nrows, const uint32_t* sb, uint32_t nsb) {
+  const uint32_t lo = j * CLU_SUB_ROWS, hi = lo + CLU_SUB_ROWS < nrows ? lo + CLU_SUB_ROWS : nrows;
+  uint32_t c = 0u;
+  bool whole = true;
+  for (uint32_t k = 0; k < CLU_SPLIT_MAX; k++) {
+    if (k >= nsb) continue;
+    c += sb[k] <= lo ? 1u : 0u;
+    whole = whole && !(sb[k] > lo && sb[k] < hi);
+  }
+  return whole ? c : CLU_SUB_STRADDLE;
+}
+
 enum CluKind : uint32_t {
   CLU_NONE = 0,     // outside the glob window: no row of the tile counts
   CLU_PINNED,       // every row in bucket b0

@@ -11,6 +11,13 @@
 // cpref[c + 1]) with coalesced 8-B loads and crows (the element's row within the tile), and takes each element's class
 // from its row index against boundary rows found with scan_lean's two-round timestamp search (256 samples, then the
 // sample gap holding each boundary): the wave reduces per (code, class) and lane 0 merges once per (tile, code, class).
+// Of a split tile only the 4,096-row sub-blocks that hold a boundary row are streamed (clu.hpp, clu_sub_class: at most
+// three): a sub-block that holds none lies in one class whatever the query, and what its passing codes contribute was
+// stored at load in the segment's sub-block area (csub / sagg, clu.hpp): lane j loads code c's csub[c][j], csub[c][j + 1]
+// and sagg[c][j] in one round and starts its per-class accumulators with them; the streamed elements are added on top,
+// then the one shuffle tree and the one merge per (tile, code, class).  LK_NO_CLU_SUB=1 (SPLIT_OK_NO_CLU_SUB), or a
+// segment without the area, streams the ranges whole: bit for bit the same MIN, MAX and integral sums, real sums within
+// the suite's bar (the double-double partials combine in another order).
 // No run staging, no chunk table, no row list, no LDS.  global_merge honours the LEAN_* flags, the -0.0 empty marker,
 // exact_sum and FLAG_MIN_NAN.  LK_NO_CLU_AGG=1 (SPLIT_OK_NO_CLU_AGG) streams pinned tiles too, with clu_reduce_pinned
 // (one merge per (tile, code)): the same rows bit for bit, the A/B and the tests' proof of which path ran.
@@ -32,6 +39,7 @@
 namespace lk {
 
 constexpr int CLU_WAVES = BLOCK / 64;   // tiles per workgroup
+typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 
 template <int AGG>
 __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
@@ -190,21 +198,48 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
 
   bool nan_seen = false;
 
-  // One passing code's range [s, s + n) of a split tile: NK classes (the in-window classes 1 .. nsb - 1, at most
-  // CLU_SPLIT_MAX - 1), U loads per lane in flight.  (A pinned tile's range: clu_reduce_pinned, below.)
-  auto stream = [&](auto nkc, auto uc, uint32_t s, uint32_t n, uint32_t dim) __attribute__((always_inline)) {
-    constexpr uint32_t NK = decltype(nkc)::value;
-    constexpr uint32_t U = decltype(uc)::value;
-    constexpr bool SPLIT = NK > 1;
-    double hi[NK], lo[NK];
-    unsigned long long ext[NK];
-    uint32_t cnt[NK];
-#pragma unroll
-    for (uint32_t k = 0; k < NK; k++) {
-      hi[k] = lo[k] = 0.0;
-      ext[k] = AGG == AGG_MIN ? ~0ull : 0ull;
-      cnt[k] = 0u;
+  // One loop over the passing codes per kind of tile, so that neither path's registers are live across the other's.
+  // Pinned, streamed (LK_NO_CLU_AGG): the reduction the copy's aggregates were built with.
+  while (!split && emask) {
+    const uint32_t c = uint32_t(__builtin_ctzll(emask));
+    emask &= emask - 1ull;
+    const uint32_t s = uni(__shfl(cs, int(c), 64)), e = uni(__shfl(ce, int(c), 64));
+    if (s >= e) continue;   // the name is absent from the tile
+    const uint32_t dim = (uni(__shfl(lut, int(c), 64)) & DIM_MASK) * stride;
+    const CluRed r = clu_reduce_pinned<AGG == AGG_SUM, AGG == AGG_MIN, AGG == AGG_MAX, 16u>(rv, s, e - s, lane, P.exact_sum != 0u);
+    nan_seen = nan_seen || r.nan;
+    if (lane == 0 && r.cnt) {
+      const unsigned long long cell = (glob_base + (unsigned long long)cc.b0) * P.ngroups + dim;
+      global_merge<AGG, false>(P, cell, r.cnt, r.cnt, r.hi, r.lo, AGG == AGG_MIN ? r.omin : r.omax);
     }
+    if (count_plan && lane == 0) pbytes += 128u * uint64_t(((e * 8u + 127u) >> 7) - ((s * 8u) >> 7));
+  }
+  if (!split) {   // uniform
+    if (AGG == AGG_MIN && __ballot(nan_seen) && lane == 0) atomicOr(P.flags, FLAG_MIN_NAN);
+    if (pbytes) atomicAdd(P.plan_bytes, (unsigned long long)pbytes);
+    return;
+  }
+
+  // A split tile's sub-block area (clu.hpp): the whole sub-blocks of a passing code hand on their stored aggregates,
+  // only the straddling ones are streamed.  LK_NO_CLU_SUB=1, or a segment without the area: the range streams whole.
+  const bool use_sub = split && Sp->clu_sub != nullptr && !(P.split_ok & SPLIT_OK_NO_CLU_SUB) && d.nrows <= tdp->nrows &&
+                       clu_sub_bytes(d.dict_n) <= Sp->clu_sub_stride && dict_n <= clu_dict_n(d.dict_n);   // uniform
+  const __amdgpu_buffer_rsrc_t rsub =
+      make_rsrc(use_sub ? Sp->clu_sub + uint64_t(t) * Sp->clu_sub_stride : nullptr, use_sub ? clu_sub_bytes(d.dict_n) : 0u);
+  const uint32_t nsub = clu_nsub(nrows);
+  // lane j: sub-block j's class, CLU_SUB_STRADDLE when its rows' classes differ (the same for every code)
+  uint32_t subc = CLU_SUB_STRADDLE;
+  if (use_sub && lane < nsub) subc = clu_sub_class(lane, nrows, sb, nsb);
+
+  // One passing code of a split tile: NK classes (the in-window classes 1 .. nsb - 1, at most CLU_SPLIT_MAX - 1) in
+  // per-lane accumulators that the sub-blocks' aggregates and the streamed ranges share, reduced and merged once.
+  constexpr uint32_t NK = CLU_SPLIT_MAX - 1u;
+  double hi[NK], lo[NK];
+  unsigned long long ext[NK];
+  uint32_t cnt[NK];
+  // the range [s, s + n) of cvals / crows into the accumulators, U loads per lane in flight
+  auto stream = [&](auto uc, uint32_t s, uint32_t n) __attribute__((always_inline)) {
+    constexpr uint32_t U = decltype(uc)::value;
     for (uint32_t i0 = 0; i0 < n; i0 += 64u * U) {
       v2u x[U];
       uint32_t r[U];
@@ -212,17 +247,17 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
       for (uint32_t u = 0; u < U; u++) {
         const uint32_t i = i0 + 64u * u + lane;
         x[u] = __builtin_amdgcn_raw_buffer_load_b64(rv, i < n ? (s + i) * 8u : OOB, 0, 0);
-        r[u] = (SPLIT && i < n) ? uint32_t(crows[s + i]) : 0u;
+        r[u] = i < n ? uint32_t(crows[s + i]) : 0u;
       }
 #pragma unroll
       for (uint32_t u = 0; u < U; u++) {
         const uint32_t i = i0 + 64u * u + lane;
         const double v = __longlong_as_double((long long)(((uint64_t)x[u].y << 32) | x[u].x));
-        const uint32_t c = SPLIT ? split_class(r[u]) : 1u;
+        const uint32_t c = split_class(r[u]);
         const bool live = i < n;
 #pragma unroll
         for (uint32_t k = 0; k < NK; k++) {
-          if (!live || c != k + 1u || (SPLIT && k + 1u >= nsb)) continue;
+          if (!live || c != k + 1u || k + 1u >= nsb) continue;
           cnt[k] += 1u;
           if (AGG == AGG_SUM) {
             if (P.exact_sum) {
@@ -241,7 +276,12 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
         }
       }
     }
-    // wave reduction per class, one merge per (tile, code, class)
+    if (count_plan && lane == 0)   // the 128-B lines of the streamed range
+      pbytes += 128u * uint64_t((((s + n) * 8u + 127u) >> 7) - ((s * 8u) >> 7)) +
+                128u * uint64_t((((s + n) * 2u + 127u) >> 7) - ((s * 2u) >> 7));
+  };
+  // wave reduction per class, one merge per (tile, code, class)
+  auto finish = [&](uint32_t dim) __attribute__((always_inline)) {
 #pragma unroll
     for (uint32_t k = 0; k < NK; k++) {
 #pragma unroll
@@ -268,28 +308,103 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
         global_merge<AGG, false>(P, cell, cnt[k], cnt[k], hi[k], lo[k], ext[k]);
       }
     }
-    if (count_plan && lane == 0) {   // the 128-B lines of the streamed ranges
-      pbytes += 128u * uint64_t((((s + n) * 8u + 127u) >> 7) - ((s * 8u) >> 7));
-      if (SPLIT) pbytes += 128u * uint64_t((((s + n) * 2u + 127u) >> 7) - ((s * 2u) >> 7));
-    }
   };
 
+  // Split tiles whose ranges stream whole (LK_NO_CLU_SUB=1, or no sub-block area): a loop of their own, as above.
+  while (!use_sub && emask) {
+    const uint32_t c = uint32_t(__builtin_ctzll(emask));
+    emask &= emask - 1ull;
+    const uint32_t s = uni(__shfl(cs, int(c), 64)), e = uni(__shfl(ce, int(c), 64));
+    if (s >= e) continue;   // the name is absent from the tile
+    const uint32_t dim = (uni(__shfl(lut, int(c), 64)) & DIM_MASK) * stride;
+#pragma unroll
+    for (uint32_t k = 0; k < NK; k++) {
+      hi[k] = lo[k] = 0.0;
+      ext[k] = AGG == AGG_MIN ? ~0ull : 0ull;
+      cnt[k] = 0u;
+    }
+    stream(std::integral_constant<uint32_t, 8u>{}, s, e - s);
+    finish(dim);
+  }
+  // Split tiles with the sub-block area.
   while (emask) {
     const uint32_t c = uint32_t(__builtin_ctzll(emask));
     emask &= emask - 1ull;
     const uint32_t s = uni(__shfl(cs, int(c), 64)), e = uni(__shfl(ce, int(c), 64));
     if (s >= e) continue;   // the name is absent from the tile
     const uint32_t dim = (uni(__shfl(lut, int(c), 64)) & DIM_MASK) * stride;
-    if (split) stream(std::integral_constant<uint32_t, CLU_SPLIT_MAX - 1u>{}, std::integral_constant<uint32_t, 8u>{}, s, e - s, dim);
-    else {   // pinned, streamed (LK_NO_CLU_AGG): the reduction the copy's aggregates were built with
-      const CluRed r = clu_reduce_pinned<AGG == AGG_SUM, AGG == AGG_MIN, AGG == AGG_MAX, 16u>(rv, s, e - s, lane, P.exact_sum != 0u);
-      nan_seen = nan_seen || r.nan;
-      if (lane == 0 && r.cnt) {
-        const unsigned long long cell = (glob_base + (unsigned long long)cc.b0) * P.ngroups + dim;
-        global_merge<AGG, false>(P, cell, r.cnt, r.cnt, r.hi, r.lo, AGG == AGG_MIN ? r.omin : r.omax);
-      }
-      if (count_plan && lane == 0) pbytes += 128u * uint64_t(((e * 8u + 127u) >> 7) - ((s * 8u) >> 7));
+#pragma unroll
+    for (uint32_t k = 0; k < NK; k++) {
+      hi[k] = lo[k] = 0.0;
+      ext[k] = AGG == AGG_MIN ? ~0ull : 0ull;
+      cnt[k] = 0u;
     }
+    // lane j: the code's elements [a, b) of sub-block j and their aggregate, one round of loads through the
+    // area's buffer resource (uniform base and entry offset, the lane's offset in one register)
+    const bool sl = lane < nsub;
+    const uint32_t co = clu_sub_csub_off(d.dict_n) + c * (CLU_SUB_MAX + 1u) * 4u;
+    uint32_t a = __builtin_amdgcn_raw_buffer_load_b32(rsub, sl ? lane * 4u : OOB, int(co), 0);
+    uint32_t b = __builtin_amdgcn_raw_buffer_load_b32(rsub, sl ? lane * 4u + 4u : OOB, int(co), 0);
+    const uint32_t go = sl ? lane * uint32_t(sizeof(CluAgg)) : OOB;
+    v2u g0, g1 = v2u{0u, 0u};   // SUM: hi, lo; MIN / MAX: the extreme
+    if (AGG == AGG_SUM) {
+      const v4u g = __builtin_amdgcn_raw_buffer_load_b128(rsub, go, int(clu_sub_sagg_off(c, 0u)), 0);
+      g0 = v2u{g.x, g.y};
+      g1 = v2u{g.z, g.w};
+    } else {
+      g0 = __builtin_amdgcn_raw_buffer_load_b64(rsub, go, int(clu_sub_sagg_off(c, 0u) + (AGG == AGG_MIN ? 16u : 24u)), 0);
+    }
+    uint32_t snan = 0u;   // MIN: the code's NaN bits (a uint16 inside an aligned word)
+    if (AGG == AGG_MIN) {
+      const uint32_t no = clu_sub_nan_off(d.dict_n) + c * 2u;
+      snan = (__builtin_amdgcn_raw_buffer_load_b32(rsub, 0u, int(no & ~3u), 0) >> ((no & 2u) * 8u)) & 0xffffu;
+    }
+    if (!sl) a = b = e;
+    b = b < e ? b : e;   // clamped to the code's range, as cpref is clamped to the tile's rows
+    b = b > s ? b : s;
+    a = a > s ? a : s;
+    a = a < b ? a : b;
+    // a whole sub-block of an in-window class starts its lane's accumulators with the stored aggregate
+    if (subc != CLU_SUB_STRADDLE && subc >= 1u && subc < nsb && a < b) {
+#pragma unroll
+      for (uint32_t k = 0; k < NK; k++) {
+        if (subc != k + 1u) continue;
+        cnt[k] = b - a;
+        if (AGG == AGG_SUM) {
+          hi[k] = __longlong_as_double((long long)(((uint64_t)g0.y << 32) | g0.x));
+          lo[k] = __longlong_as_double((long long)(((uint64_t)g1.y << 32) | g1.x));
+        } else {
+          ext[k] = ((unsigned long long)g0.y << 32) | g0.x;
+        }
+      }
+      if (AGG == AGG_MIN && ((snan >> lane) & 1u)) nan_seen = true;
+    }
+    // the straddling sub-blocks' elements (at most CLU_SPLIT_MAX - 1 sub-blocks hold a boundary inside the tile)
+    // are streamed on top; their ranges are taken into uniform registers first, so a / b end here
+    unsigned long long strad = __ballot(sl && subc == CLU_SUB_STRADDLE && a < b);
+    uint32_t ja[CLU_SPLIT_MAX], jn[CLU_SPLIT_MAX];
+#pragma unroll
+    for (uint32_t q = 0; q < CLU_SPLIT_MAX; q++) {
+      ja[q] = jn[q] = 0u;
+      if (strad) {   // uniform
+        const int j = __builtin_ctzll(strad);
+        strad &= strad - 1ull;
+        ja[q] = uni(__shfl(a, j, 64));
+        jn[q] = uni(__shfl(b, j, 64)) - ja[q];
+      }
+    }
+#pragma unroll 1
+    for (uint32_t q = 0; q < CLU_SPLIT_MAX; q++) {
+      const uint32_t qa = q == 0u ? ja[0] : q == 1u ? ja[1] : q == 2u ? ja[2] : ja[3];
+      const uint32_t qn = q == 0u ? jn[0] : q == 1u ? jn[1] : q == 2u ? jn[2] : jn[3];
+      if (qn) stream(std::integral_constant<uint32_t, 8u>{}, qa, qn);
+    }
+    if (count_plan && lane == 0) {   // the 128-B lines of the csub / sagg entries read (MIN: and of the code's NaN bits)
+      const uint32_t o0 = clu_sub_csub_off(d.dict_n) + c * (CLU_SUB_MAX + 1u) * 4u;
+      pbytes += 128u * uint64_t(((o0 + (nsub + 1u) * 4u + 127u) >> 7) - (o0 >> 7)) +
+                128u * uint64_t((nsub * uint32_t(sizeof(CluAgg)) + 127u) >> 7) + (AGG == AGG_MIN ? 128u : 0u);
+    }
+    finish(dim);
   }
   if (AGG == AGG_MIN && __ballot(nan_seen) && lane == 0) atomicOr(P.flags, FLAG_MIN_NAN);
   if (pbytes) atomicAdd(P.plan_bytes, (unsigned long long)pbytes);

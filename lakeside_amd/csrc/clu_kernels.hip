@@ -6,7 +6,11 @@
 // Then the per-code aggregates (`cagg`, the NaN mask): a wave takes codes w, w + 4, ... and reduces each one's range
 // of the cvals the workgroup has just written with clu_reduce_pinned (clu_reduce.hpp) -- the function scan_clu streams
 // a pinned tile's range with, so the stored triple is what that stream hands global_merge, bit for bit.
-// Every global store is clamped to the tile's block, every stream read goes through a buffer resource.
+// Then the segment's sub-block area (clu.hpp: csub, sagg, the per-code NaN bits), for scan_clu's split tiles: pass 2
+// walks the rows in order, so at every step that opens a 4,096-row sub-block `next[c]` is code c's first element of
+// that sub-block; behind the cagg pass' fences the (code, sub-block) ranges are reduced with the same function, spread
+// over the four waves.
+// Every global store is clamped to the tile's block or sub-block area, every stream read goes through a buffer resource.
 #include <hip/hip_runtime.h>
 
 #include "clu_reduce.hpp"
@@ -23,6 +27,8 @@ __global__ __launch_bounds__(BLOCK) void clu_build(CluBuild B) {
   __shared__ uint32_t wcnt[NW][64];    // the step's rows per (wave, code)
   __shared__ uint32_t cst[65];         // cpref (the aggregate pass reads the ranges from here)
   __shared__ unsigned long long nanm;  // bit c: a NaN among code c's values
+  __shared__ uint32_t snan[64];        // per code, bit j: a NaN among its elements of sub-block j
+  __shared__ uint32_t lsub[64][CLU_SUB_MAX + 1u];   // csub (the sub-block pass reads the ranges from here)
   const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
   const uint32_t t = blockIdx.x;
   if (t >= B.ntiles) return;
@@ -41,7 +47,13 @@ __global__ __launch_bounds__(BLOCK) void clu_build(CluBuild B) {
   uint32_t* cpref = reinterpret_cast<uint32_t*>(blk);
   unsigned long long* cvals = reinterpret_cast<unsigned long long*>(blk + clu_vals_off(dict_n));
   uint16_t* crows = reinterpret_cast<uint16_t*>(blk + clu_rows_off(nrows, dict_n));
+  // the tile's sub-block area (clu.hpp): every store below is clamped to it
+  const bool has_sub = B.sub != nullptr && clu_sub_bytes(dict_n) <= B.sub_stride;   // uniform
+  uint8_t* sblk = has_sub ? B.sub + size_t(t) * B.sub_stride : nullptr;
+  uint32_t* csub = has_sub ? reinterpret_cast<uint32_t*>(sblk + clu_sub_csub_off(dict_n)) : nullptr;
+  const uint32_t nsub = clu_nsub(nrows);
 
+  if (tid < 64u) snan[tid] = 0u;
   for (uint32_t i = tid; i < nr; i += BLOCK) {
     const RunDesc r = B.name_runs[tn->run_lo + i];
     runs[i] = LRun{r.start, r.off_lit, r.value};
@@ -77,6 +89,12 @@ __global__ __launch_bounds__(BLOCK) void clu_build(CluBuild B) {
 
   // pass 2: 256 rows per step, in row order
   for (uint32_t r0 = 0; r0 < nrows; r0 += BLOCK) {
+    // a step that opens sub-block j: next[c] is code c's first element of a row >= CLU_SUB_ROWS * j, that is csub[c][j]
+    if ((r0 & (CLU_SUB_ROWS - 1u)) == 0u && tid < dict_n) {
+      const uint32_t j = r0 / CLU_SUB_ROWS;   // < CLU_SUB_MAX: r0 < nrows <= TILE_ROWS
+      lsub[tid][j] = next[tid];
+      if (has_sub) csub[tid * (CLU_SUB_MAX + 1u) + j] = next[tid];
+    }
     const uint32_t r = r0 + tid;
     const bool valid = r < nrows;
     const uint32_t c = valid ? code_of(r) : 0u;
@@ -115,6 +133,12 @@ __global__ __launch_bounds__(BLOCK) void clu_build(CluBuild B) {
     __syncthreads();
   }
 
+  if (tid < dict_n)   // csub's entries past the tile's sub-blocks repeat cpref[c + 1]
+    for (uint32_t j = nsub; j <= CLU_SUB_MAX; j++) {
+      lsub[tid][j] = cst[tid + 1u];
+      if (has_sub) csub[tid * (CLU_SUB_MAX + 1u) + j] = cst[tid + 1u];
+    }
+
   // pass 3: cagg.  The cvals were stored by other lanes: each thread's stores are fenced before the barrier, and the
   // reading waves fence again behind it before their buffer loads.
   __threadfence();
@@ -132,8 +156,28 @@ __global__ __launch_bounds__(BLOCK) void clu_build(CluBuild B) {
       if (r.nan) atomicOr(&nanm, 1ull << c);
     }
   }
+  // pass 4: sagg, the (code, sub-block) ranges spread over the waves, reduced with the same function (behind the same
+  // fences); sub-blocks past the tile's rows get the empty range's entry.  4 loads per lane in flight where cagg and
+  // scan_clu use 16: a range here is about 256 elements, and the depth changes neither which elements a lane takes
+  // (l, l + 64, ...) nor their order, so the result is the one any depth gives
+  if (has_sub) {   // uniform
+    CluAgg* sagg = reinterpret_cast<CluAgg*>(sblk);
+    for (uint32_t p = w; p < dict_n * CLU_SUB_MAX; p += NW) {   // uniform per wave; p = c * CLU_SUB_MAX + j
+      const uint32_t c = p / CLU_SUB_MAX, j = p % CLU_SUB_MAX;
+      uint32_t se = lsub[c][j + 1u], ss = lsub[c][j];
+      se = se < nrows ? se : nrows;
+      ss = ss < se ? ss : se;
+      if (j >= nsub) ss = se;
+      const CluRed r = clu_reduce_pinned<true, true, true, 4u>(rcv, uni(ss), uni(se - ss), lane, false);
+      if (lane == 0u) {
+        sagg[p] = CluAgg{r.hi, r.lo, r.omin, r.omax};
+        if (r.nan) atomicOr(&snan[c], 1u << j);
+      }
+    }
+  }
   __syncthreads();
   if (tid == 0u) *reinterpret_cast<unsigned long long*>(blk + CLU_NAN_OFF) = nanm;
+  if (has_sub && tid < dict_n) reinterpret_cast<uint16_t*>(sblk + clu_sub_nan_off(dict_n))[tid] = uint16_t(snan[tid]);
 }
 
 }  // namespace

@@ -23,6 +23,25 @@ extern "C" uint64_t lk_clu_block_bytes(uint32_t nrows, uint32_t dict_n, uint32_t
   return lk::clu_block_bytes(nrows, dict_n);
 }
 
+extern "C" uint32_t lk_clu_sub_bytes(uint32_t nrows, uint32_t dict_n, uint32_t c, uint32_t j, uint32_t* nsub,
+                                     uint32_t* sub_rows, uint32_t* sub_max, uint32_t* sagg_off, uint32_t* csub_off,
+                                     uint32_t* nan_off) {
+  if (nsub) *nsub = lk::clu_nsub(nrows);
+  if (sub_rows) *sub_rows = lk::CLU_SUB_ROWS;
+  if (sub_max) *sub_max = lk::CLU_SUB_MAX;
+  if (sagg_off) *sagg_off = lk::clu_sub_sagg_off(c, j);
+  if (csub_off) *csub_off = lk::clu_sub_csub_off(dict_n);
+  if (nan_off) *nan_off = lk::clu_sub_nan_off(dict_n);
+  return lk::clu_sub_bytes(dict_n);
+}
+
+extern "C" uint32_t lk_clu_sub_sim(uint32_t nrows, const uint32_t* sb, uint32_t nsb, uint32_t* cls) {
+  using namespace lk;
+  const uint32_t n = clu_nsub(nrows);
+  for (uint32_t j = 0; j < n; j++) cls[j] = clu_sub_class(j, nrows, sb, nsb);
+  return n;
+}
+
 extern "C" int lk_clu_segment_taken(int all_copies_sorted, int64_t widest, int64_t step) {
   return lk::clu_segment_taken(all_copies_sorted != 0, widest, step) ? 1 : 0;
 }

@@ -453,6 +453,7 @@ Segment::~Segment() {
   if (d_data) (void)hipFree(d_data);
   if (d_meta) (void)hipFree(d_meta);
   if (d_clu) (void)hipFree(d_clu);
+  if (d_clu_sub) (void)hipFree(d_clu_sub);
 }
 
 int Engine::load_thread_count() const {
@@ -566,7 +567,7 @@ void Engine::build_cluster(Segment& S) {
   if (!N.is_string || V.is_string || N.tcols.size() != nt || V.tcols.size() != nt) return;
   std::vector<CluTile> desc(nt, CluTile{CLU_NO_COPY, 0u, 0u});
   size_t off = align_up(nt * sizeof(CluTile), CLU_BLOCK_ALIGN);
-  uint32_t copies = 0;
+  uint32_t copies = 0, max_dict_n = 1;
   bool all_sorted = true;
   int64_t widest = -1;
   for (size_t t = 0; t < nt; t++) {
@@ -579,6 +580,7 @@ void Engine::build_cluster(Segment& S) {
     if (ok) {
       desc[t] = CluTile{off, td.nrows, a.dict_n};
       off += size_t(clu_block_bytes(td.nrows, a.dict_n));
+      max_dict_n = std::max(max_dict_n, uint32_t(a.dict_n));
       copies++;
     }
     if (!ok || !(td.pad & TILE_TS_SORTED) || td.ts_min > td.ts_max) all_sorted = false;
@@ -594,6 +596,16 @@ void Engine::build_cluster(Segment& S) {
     return;
   }
   S.clu_bytes = off;
+  // The sub-block area: a fixed stride per tile, the segment's largest dict_n.  Without it (the allocation failed) the
+  // segment keeps its copy and its split tiles stream whole: not an error.
+  S.clu_sub_stride = clu_sub_bytes(max_dict_n);
+  if (hipMalloc(&S.d_clu_sub, nt * size_t(S.clu_sub_stride)) != hipSuccess) {
+    (void)hipGetLastError();
+    S.d_clu_sub = nullptr;
+    S.clu_sub_stride = 0;
+  } else {
+    S.clu_sub_bytes = nt * size_t(S.clu_sub_stride);
+  }
   S.d_clu_desc = reinterpret_cast<const CluTile*>(S.d_clu);
   HIP_CHECK(hipMemcpyAsync(S.d_clu, desc.data(), nt * sizeof(CluTile), hipMemcpyHostToDevice, load_stream));
   CluBuild B{};
@@ -603,6 +615,8 @@ void Engine::build_cluster(Segment& S) {
   B.name_runs = N.d_runs;
   B.desc = S.d_clu_desc;
   B.clu = S.d_clu;
+  B.sub = S.d_clu_sub;
+  B.sub_stride = S.clu_sub_stride;
   B.ntiles = uint32_t(nt);
   HIP_CHECK(launch_clu_build(B, load_stream));
   HIP_CHECK(hipStreamSynchronize(load_stream));   // `desc` is freed on return

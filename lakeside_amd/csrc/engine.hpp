@@ -40,11 +40,17 @@ struct Segment : SegmentData {
   uint8_t* d_clu = nullptr;
   const CluTile* d_clu_desc = nullptr;
   size_t clu_bytes = 0;
+  // The copy's sub-block area (clu.hpp, clu_sub_bytes): a second allocation, clu_sub_stride bytes per tile (the
+  // segment's largest dict_n), built by the same clu_build launch; null when its allocation failed -- the segment keeps
+  // its copy and scan_clu streams its split tiles whole.
+  uint8_t* d_clu_sub = nullptr;
+  size_t clu_sub_bytes = 0;
+  uint32_t clu_sub_stride = 0;
   int clu_name_col = -1, clu_val_col = -1;
   uint32_t clu_tiles = 0;
   bool clu_all_sorted = false;
   int64_t clu_widest = -1;
-  size_t hbm_bytes() const { return data_bytes + meta_bytes + clu_bytes; }   // the segment's cache weight
+  size_t hbm_bytes() const { return data_bytes + meta_bytes + clu_bytes + clu_sub_bytes; }   // the segment's cache weight
   bool from_put = false;                         // registered by lk_segment_put (its key is not a file path)
   std::atomic<uint64_t> last_use{0};             // LRU clock value of the last lookup (cache eviction)
   struct Engine* engine = nullptr;               // whose dictionaries its remaps reference (refs released at ~Segment)

@@ -353,6 +353,8 @@ void setup_scan(const EvalCall& C, const Plan& pl, DevState& dv) {
   dv.P.split_ok = getenv("LK_NO_SPLIT") ? 0u : 1u;   // env: A/B only
   // LK_NO_CLU_AGG=1 (read per call: A/B and the tests' proof of the path): scan_clu streams its pinned tiles
   if (dv.P.split_ok && getenv("LK_NO_CLU_AGG")) dv.P.split_ok |= SPLIT_OK_NO_CLU_AGG;
+  // LK_NO_CLU_SUB=1 (read per call, independent of the above): scan_clu streams its split tiles' ranges whole
+  if (dv.P.split_ok && getenv("LK_NO_CLU_SUB")) dv.P.split_ok |= SPLIT_OK_NO_CLU_SUB;
   if (pl.fp.vleaf && !pl.sg.qsegs.empty()) {   // scan_lean tests the value leaves of every row its string conjuncts pass
     dv.P.nvl = uint32_t(pl.fp.nleaves.size());
     dv.P.vtab = pl.fp.vtab;

@@ -254,6 +254,8 @@ struct CluBuild {
   const RunDesc* name_runs;
   const CluTile* desc;             // per tile (device copy)
   uint8_t* clu;                    // the copy area
+  uint8_t* sub;                    // the sub-block area (clu.hpp, clu_sub_bytes), sub_stride bytes per tile; null: none
+  uint32_t sub_stride;
   uint32_t ntiles;
 };
 hipError_t launch_clu_build(const CluBuild& B, hipStream_t stream);

@@ -146,6 +146,11 @@ struct QSeg {
   // column 1 its value column; eval_plan.cpp plan_segments / plan_cluster); null otherwise
   const CluTile* clu;
   const uint8_t* clu_base;
+  // the copy's sub-block area (clu.hpp, clu_sub_bytes): tile t's at clu_sub + t * clu_sub_stride; null: the segment
+  // has none, its split tiles stream their ranges whole
+  const uint8_t* clu_sub;
+  uint32_t clu_sub_stride;
+  uint32_t pad1;
 };
 
 enum Agg : int { AGG_SUM = 0, AGG_MIN = 1, AGG_MAX = 2, AGG_COUNT = 3 };
@@ -249,6 +254,8 @@ struct QParams {
   VLeaf vl[VLEAF_MAX];
 };
 constexpr uint32_t SPLIT_OK_NO_CLU_AGG = 2u;   // QParams::split_ok bit 1
+constexpr uint32_t SPLIT_OK_NO_CLU_SUB = 4u;   // bit 2 (env LK_NO_CLU_SUB, A/B and tests): scan_clu streams a split
+                                               // tile's ranges whole instead of merging its whole sub-blocks' aggregates
 // scan_lean's direct table: LDS words by late-column count NL (the hash table's 8 KB for NL >= 1, so the kernels keep
 // their occupancy), at most LEAN_DIR_MAXSPAN buckets
 constexpr uint32_t LEAN_DIR_WORDS0 = 1536;
