@@ -13,7 +13,7 @@
  * library until lk_result_free.  Calls on one engine are thread-safe and re-entrant: each evaluation leases its
  * own context (HIP stream, workspaces; up to "max_calls" in flight), so calls from several threads run
  * concurrently, as the worker's glob queries do (Commons.scala:371-372); only distributed calls
- * (lk_eval_pushdown_dist) are serialised, to keep every rank's collectives in one order, and a dictionary
+ * (lk_eval_pushdown_dist, lk_eval_formula_dist) are serialised, to keep every rank's collectives in one order, and a dictionary
  * compaction (see lk_engine_create) runs between loads / evaluations, never under one.
  *
  * Errors: a failure that belongs to one glob's DuckDB query in the reference -- a missing or unreadable segment,
@@ -108,7 +108,7 @@ int lk_eval_pushdown(lk_engine* e, const char* push_down_json, const char* const
  * first appearance; a row with empty tags answers NULL in every column.  lk_result_globs is all zeros.  The bulk tag
  * export does not apply to formula results: lk_result_group_ids returns NULL and lk_result_num_group_columns 0 -- read
  * tags with lk_result_tag_value.  lk_result_stats carries "formula": {"mode": "dense"|"hash", "cells", "operands_on_device",
- * "operands_uploaded", "regrows"}.
+ * "operands_uploaded", "regrows", "world", "rank", "operands"} (the last three: see lk_eval_formula_dist).
  * LK_ERR_ARG: malformed formula (unknown variable, unbalanced parentheses, a single term), expressions with different
  * steps.  LK_ERR_UNSUPPORTED (the message names the rule): `^`, relational operators, unary signs; expressions whose
  * groupBy sets differ; an expression without a chart, a tag query, extract / compute, metrics percentiles.
@@ -165,6 +165,20 @@ int lk_comm_init_host(lk_engine* e, int world, int rank, lk_allgather_fn fn, voi
  * (other ranks get an empty result). shard == NULL: i % world. */
 int lk_eval_pushdown_dist(lk_engine* e, const char* push_down_json, const char* const* paths, size_t n_paths,
                           const int32_t* shard, int glob_size, lk_result** out);
+/* lk_eval_formula with a rank per pod: replaces query-api's fan-out of every base expression of a formula to the pods,
+ * the merge of their streams (mergeSortedSource / TimeGroupedSketchAggregator) and Formula.eval over the merged sides
+ * (QueryEngineV2.evaluateFormula, query-api/.../engine/QueryEngineV2.scala:310-389; Formula.scala:32-69).
+ * formula_json: what lk_eval_formula takes; an expression may carry "shard": [..], one rank per path with the meaning
+ * of lk_eval_pushdown_dist's shard (absent: i % world).  A shard of the wrong length or a rank outside [0, world) is
+ * LK_ERR_ARG, decided -- like every refusal lk_eval_formula makes from the request -- before any collective, so every
+ * rank must pass the same formula, the same variable names and the same pushDowns.  Each referenced expression is one
+ * sharded merged evaluation (every rank takes part in each, in ascending byte order of the variable names) whose rows
+ * land on rank 0 and stay on its device; rank 0 joins them and returns what lk_eval_formula returns over all the paths
+ * (rows, tag columns, lk_result_globs all zero, no bulk export).  Every other rank gets LK_OK and an empty result that
+ * still carries stats.  A failure of one expression fails the call on every rank at that expression.
+ * lk_result_stats' "formula" also carries "world", "rank" and "operands": [{"var", "reduce", "rows", "kept"}] in
+ * evaluation order (as lk_eval_formula's does, with world 1).  Without lk_comm_init*: LK_ERR_ARG. */
+int lk_eval_formula_dist(lk_engine* e, const char* formula_json, int glob_size, lk_result** out);
 
 #ifdef __cplusplus
 }

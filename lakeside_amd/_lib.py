@@ -57,6 +57,7 @@ SIGNATURES = [
     ("lk_comm_init", _c.c_int, [_P, _c.c_void_p, _c.c_int, _c.c_int]),
     ("lk_eval_pushdown_dist", _c.c_int, [_P, _c.c_char_p, _c.POINTER(_c.c_char_p), _c.c_size_t,
                                          _c.POINTER(_c.c_int32), _c.c_int, _c.POINTER(_P)]),
+    ("lk_eval_formula_dist", _c.c_int, [_P, _c.c_char_p, _c.c_int, _c.POINTER(_P)]),
 ]
 
 # int (*lk_allgather_fn)(void* user, const void* send, size_t bytes, void* recv)

@@ -14,7 +14,7 @@
 namespace lk {
 int evaluate(Engine& E, const std::string& json, const char* const* paths, size_t n_paths, int glob_size,
              unsigned flags, const int32_t* shard, bool dist, lk_result* res);
-int evaluate_formula(Engine& E, const std::string& json, int glob_size, lk_result* res);
+int evaluate_formula(Engine& E, const std::string& json, int glob_size, bool dist, lk_result* res);
 }
 
 namespace {
@@ -233,7 +233,7 @@ int lk_eval_pushdown_dist(lk_engine* e, const char* push_down_json, const char* 
   return eval_common(e, push_down_json, paths, n_paths, shard, glob_size, LK_MERGED, true, out);
 }
 
-int lk_eval_formula(lk_engine* e, const char* formula_json, int glob_size, lk_result** out) {
+static int formula_common(lk_engine* e, const char* formula_json, int glob_size, bool dist, lk_result** out) {
   if (!e || !formula_json || !out) return LK_ERR_ARG;
   *out = nullptr;
   return guarded([&] {
@@ -241,7 +241,7 @@ int lk_eval_formula(lk_engine* e, const char* formula_json, int glob_size, lk_re
     std::shared_lock<std::shared_mutex> gen(e->e->gen_mu);
     auto* r = new lk_result();
     try {
-      lk::evaluate_formula(*e->e, formula_json, glob_size, r);
+      lk::evaluate_formula(*e->e, formula_json, glob_size, dist, r);
     } catch (...) {
       delete r;
       throw;
@@ -249,6 +249,14 @@ int lk_eval_formula(lk_engine* e, const char* formula_json, int glob_size, lk_re
     *out = r;
     return LK_OK;
   });
+}
+
+int lk_eval_formula(lk_engine* e, const char* formula_json, int glob_size, lk_result** out) {
+  return formula_common(e, formula_json, glob_size, false, out);
+}
+
+int lk_eval_formula_dist(lk_engine* e, const char* formula_json, int glob_size, lk_result** out) {
+  return formula_common(e, formula_json, glob_size, true, out);
 }
 
 size_t lk_result_num_rows(const lk_result* r) { return r ? r->nrows : 0; }

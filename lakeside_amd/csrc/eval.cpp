@@ -397,7 +397,7 @@ void setup_scan(const EvalCall& C, const Plan& pl, DevState& dv) {
   // the step grid, MIN over NaN) discards the speculative rows.
   dv.out_keys = pl.cs.ncells == 0 ? 0 : (pl.qs.per_glob_rows ? pl.cs.ncells : (pl.cs.collapse ? pl.cs.nbuckets : pl.cs.nbuckets * pl.dp.ngroups));
   dv.keep_dev = (C.flags & kEvalKeepDevice) != 0;
-  if (dv.keep_dev && (C.dist || pl.qs.per_glob_rows || pl.qs.sketch || pl.qs.ces || pl.qs.tagq))
+  if (dv.keep_dev && (pl.qs.per_glob_rows || pl.qs.sketch || pl.qs.ces || pl.qs.tagq))
     throw PlanError(LK_ERR_DEVICE, "internal: rows kept on the device are merged aggregate rows");
   dv.fast_final = !dv.keep_dev && !C.dist && !pl.cs.hash_mode && !pl.qs.sketch && !pl.qs.ces && !pl.cs.rekey && pl.cs.ncells && dv.out_keys <= (uint64_t(1) << 20) &&
                           !getenv("LK_NO_FAST_FINAL");
@@ -875,7 +875,8 @@ void reduce_tables(const EvalCall& C, const Plan& pl, DevState& dv) {
       // every PCIe link of the node at once (otherwise: all rows into rank 0's device, then over its one link).
       const char* se = getenv("LK_SHM_EMIT");
       EmitTarget ET;
-      if (total_rows && !(se && *se == '0')) ET = comm_emit_begin(C.E, C.X, size_t(total_rows) * 20);
+      // (a formula's kept operand: the rows are gathered into rank 0's device below and never touch the host block)
+      if (total_rows && !dv.keep_dev && !(se && *se == '0')) ET = comm_emit_begin(C.E, C.X, size_t(total_rows) * 20);
       if (ET.ok) {
         const size_t N = size_t(total_rows), o = size_t(noff[size_t(pl.gp.rank)]);
         int wst = ET.mapped ? 0 : LK_ERR_DEVICE;
@@ -929,7 +930,15 @@ void reduce_tables(const EvalCall& C, const Plan& pl, DevState& dv) {
             r2.push_back(Piece{j, rb + size_t(a) * total_rows * 8 + noff[size_t(j)] * wcol[a], size_t(ncnt[size_t(j)]) * wcol[a]});
       comm_exchange(C.E, C.X, s2, r2);
       comm_throw_pending(C.X);   // (host transport) a failed unpacking of the last round; no collective follows
-      if (pl.gp.rank == 0) {
+      if (pl.gp.rank == 0 && dv.keep_dev) {   // the rows stay on the device: out of the call's workspace, device to device
+        dv.nrows_out = uint32_t(total_rows);
+        if (dv.nrows_out) {
+          HIP_TRY(hipMalloc(&C.res->dev_rows, size_t(dv.nrows_out) * 20 + 64));
+          HIP_TRY(hipMemcpyAsync(C.res->dev_rows, rb, size_t(dv.nrows_out) * 20, hipMemcpyDeviceToDevice, dv.st));
+          HIP_TRY(hipStreamSynchronize(dv.st));
+        }
+        dv.rows_done = true;
+      } else if (pl.gp.rank == 0) {
         dv.nrows_out = uint32_t(total_rows);
         C.res->alloc_rows(dv.nrows_out, false);
         if (dv.nrows_out) {
@@ -1203,7 +1212,7 @@ void write_rows(const EvalCall& C, const Plan& pl, DevState& dv) {
       if (C.res->keep_sketches) C.res->dd_objs.push_back(k.sk);
     }
   } else if (dv.keep_dev) {
-    if (dv.nrows_out) {
+    if (dv.nrows_out && !dv.rows_done) {   // (rows_done: the key-range reduce left them in dev_rows)
       const size_t n = dv.nrows_out;
       HIP_TRY(hipMalloc(&C.res->dev_rows, n * 20 + 64));
       uint8_t* ob = static_cast<uint8_t*>(C.res->dev_rows);
@@ -1322,7 +1331,7 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   // Distributed calls issue collectives: one at a time per engine, in the same order on every rank.  Every call
   // runs on its own context (stream, workspaces), so local calls from several threads overlap.
   std::unique_lock<std::mutex> comm_lock;
-  if (dist) comm_lock = std::unique_lock<std::mutex>(E.comm_mu);
+  if (dist && !(flags & kEvalCommHeld)) comm_lock = std::unique_lock<std::mutex>(E.comm_mu);   // (a formula holds it over its operands)
   CtxLease X(E);
   X->pend_code = 0;
   X->pend_msg.clear();
@@ -1450,9 +1459,18 @@ int evaluate(Engine& E, const std::string& json, const char* const* paths, size_
 }
 
 // Operand of a formula (formula_eval.cpp): one merged evaluation whose rows stay on the device (kEvalKeepDevice).
+// Distributed (lk_eval_formula_dist, which holds comm_mu): the sharded evaluation, rank 0's rows kept on its device.
 int evaluate_keep_device(Engine& E, const std::shared_ptr<const Request>& Rp, const char* const* paths, size_t n_paths,
-                         int glob_size, lk_result* res) {
-  return evaluate_req(E, Rp, paths, n_paths, glob_size, LK_MERGED | kEvalKeepDevice, nullptr, false, res);
+                         int glob_size, const int32_t* shard, bool dist, lk_result* res) {
+  return evaluate_req(E, Rp, paths, n_paths, glob_size, LK_MERGED | kEvalKeepDevice | (dist ? kEvalCommHeld : 0u), shard,
+                      dist, res);
+}
+
+// Operand of a distributed formula whose values are assembled on the host (`p<NN>`, ces): the sharded merged
+// evaluation, its parts included, under the comm_mu its caller holds.
+int evaluate_comm_held(Engine& E, const std::string& json, const char* const* paths, size_t n_paths, int glob_size,
+                       const int32_t* shard, lk_result* res) {
+  return evaluate(E, json, paths, n_paths, glob_size, LK_MERGED | kEvalCommHeld, shard, true, res);
 }
 
 }  // namespace lk

@@ -28,9 +28,13 @@ enum Redo : unsigned { REDO_METRICS_RAW = 1u, REDO_MIN_APART = 2u };
 constexpr unsigned kEvalDistPerGlob = 1u << 30;
 // internal evaluation flag (evaluate_keep_device, the operands of lk_eval_formula): merged rows finalized into a device
 // buffer the result owns (lk_result::dev_rows) instead of the host block -- no speculative finalize, no small-table
-// epilogue, no key_bits / ts_runs host expansion, no device->host copy.  Off for every C ABI entry point but
-// lk_eval_formula.
+// epilogue, no key_bits / ts_runs host expansion, no device->host copy.  Distributed: rank 0 keeps the merged rows
+// whichever reduce path the tables took, the other ranks keep nothing.  Off for every C ABI entry point but
+// lk_eval_formula and lk_eval_formula_dist.
 constexpr unsigned kEvalKeepDevice = 1u << 29;
+// internal evaluation flag (the operands of lk_eval_formula_dist): the caller holds Engine::comm_mu for a whole sequence
+// of distributed evaluations, so evaluate_once does not take it
+constexpr unsigned kEvalCommHeld = 1u << 27;
 // internal evaluation flag: the per-glob MAX rows of a metrics `p<NN>` (evaluate_metrics_pct), which takes no numeric
 // groupBy (plan_numeric_group_bys)
 constexpr unsigned kEvalMetricsPct = 1u << 28;

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/lakeside_gpu.h"
+#include "comm.hpp"
 #include "engine.hpp"
 #include "evalutil.hpp"
 #include "formula.hpp"
@@ -44,7 +45,9 @@ namespace lk {
 int evaluate(Engine& E, const std::string& json, const char* const* paths, size_t n_paths, int glob_size,
              unsigned flags, const int32_t* shard, bool dist, lk_result* res);
 int evaluate_keep_device(Engine& E, const std::shared_ptr<const Request>& Rp, const char* const* paths, size_t n_paths,
-                         int glob_size, lk_result* res);
+                         int glob_size, const int32_t* shard, bool dist, lk_result* res);
+int evaluate_comm_held(Engine& E, const std::string& json, const char* const* paths, size_t n_paths, int glob_size,
+                       const int32_t* shard, lk_result* res);
 
 namespace {
 
@@ -138,6 +141,7 @@ struct Operand {
   std::string var;
   std::shared_ptr<const Request> R;
   std::vector<std::string> paths;
+  std::vector<int32_t> shard;   // distributed: the rank of every path ("shard"); empty: i % world
   std::shared_ptr<lk_result> res;
   bool uploaded = false;
   int xform = FX_XF_NONE;
@@ -149,7 +153,12 @@ using TagList = std::vector<std::pair<std::string, std::string>>;
 
 }  // namespace
 
-int evaluate_formula(Engine& E, const std::string& json, int glob_size, lk_result* res) {
+// Distributed (lk_eval_formula_dist; DESIGN.md §7.6 "Distributed"): a rank is a pod.  Every operand is one sharded merged
+// evaluation whose rows land on rank 0 (kept on its device, or uploaded by it), the join runs on rank 0 alone.  comm_mu is
+// held for the whole call; the operands run in ascending byte order of their variable names, each closed by one
+// agreement of the ranks' outcomes, so every rank issues the same collectives and all fail at the same operand.
+// Everything decided before the first collective -- the parser, the gate, the shard check -- reads the request alone.
+int evaluate_formula(Engine& E, const std::string& json, int glob_size, bool dist, lk_result* res) {
   const auto t_start = std::chrono::steady_clock::now();
   if (glob_size <= 0) glob_size = 10;
   Json top = Json::parse(json);
@@ -182,13 +191,14 @@ int evaluate_formula(Engine& E, const std::string& json, int glob_size, lk_resul
   if (ops.size() > size_t(FX_MAXLEAF))
     throw PlanError(LK_ERR_UNSUPPORTED, "formula: more than " + std::to_string(FX_MAXLEAF) + " expressions referenced");
 
+  const int world = dist ? comm_world(E) : 1, rank = dist ? comm_rank(E) : 0;
   char fstats[512];
   auto finish_empty = [&]() {
     res->exemplar = true;
     snprintf(fstats, sizeof(fstats),
              "{\"scan_ms\":0,\"total_ms\":%.6f,\"rows_scanned\":0,\"cells\":0,\"formula\":{\"mode\":\"dense\",\"cells\":0,"
-             "\"operands_on_device\":0,\"operands_uploaded\":0,\"regrows\":0}}",
-             ms_since(t_start));
+             "\"operands_on_device\":0,\"operands_uploaded\":0,\"regrows\":0,\"world\":%d,\"rank\":%d,\"operands\":[]}}",
+             ms_since(t_start), world, rank);
     res->stats = fstats;
     return int(LK_OK);
   };
@@ -210,6 +220,16 @@ int evaluate_formula(Engine& E, const std::string& json, int glob_size, lk_resul
       for (auto& p : ps->arr) o.paths.push_back(p.scalar_text());
     if (o.paths.size() != o.R->segments.size())
       throw PlanError(LK_ERR_ARG, "formula: expression " + o.var + ": paths must match segmentRequests");
+    if (const Json* sh = ex.get("shard"); dist && sh && sh->kind != Json::Null) {
+      if (!sh->is_arr() || sh->arr.size() != o.paths.size())
+        throw PlanError(LK_ERR_ARG, "formula: expression " + o.var + ": shard must have one rank per path");
+      for (auto& v : sh->arr) {
+        const int64_t r = v.as_i64();
+        if (r < 0 || r >= world)
+          throw PlanError(LK_ERR_ARG, "formula: expression " + o.var + ": shard rank " + std::to_string(r) + " outside the world");
+        o.shard.push_back(int32_t(r));
+      }
+    }
     const Request& R = *o.R;
     if (R.is_tag_query) refuse("expression " + o.var + " is a tag query");
     if (!R.has_chart) refuse("expression " + o.var + " has no chart (an exemplar query has no value to combine)");
@@ -236,51 +256,108 @@ int evaluate_formula(Engine& E, const std::string& json, int glob_size, lk_resul
     refuse("more than " + std::to_string(FX_MAXCOL) + " groupBy columns");
   const double secs = double(step / 1000);   // the Long quotient stepInMillis / 1000 (ASTUtils.scala:192)
 
+  if (dist && !E.comm) throw PlanError(LK_ERR_ARG, "lk_comm_init has not been called");
+
   // ---- operands: merged rows (ts, value, group id) on the device ----
-  HIP_TRY(hipSetDevice(E.device));
   unsigned long long rows_scanned = 0;
   double scan_ms = 0;
   size_t n_dev = 0, n_up = 0;
-  for (Operand& o : ops) {
+  // evaluated in ascending byte order of the variable names: the order of a distributed call's collectives must not
+  // depend on how a rank's caller ordered the JSON object (leaf numbers and a constant's tags keep reading `expressions`)
+  std::vector<size_t> order(ops.size());
+  for (size_t k = 0; k < ops.size(); k++) order[k] = k;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return ops[a].var < ops[b].var; });
+  std::unique_lock<std::mutex> comm_lock;
+  if (dist) comm_lock = std::unique_lock<std::mutex>(E.comm_mu);   // one hold over every operand's collectives
+  std::string op_stats;   // "operands": per variable, in evaluation order
+  for (size_t k : order) {
+    Operand& o = ops[k];
     o.res = std::make_shared<lk_result>();
     std::vector<const char*> pp;
     for (auto& p : o.paths) pp.push_back(p.c_str());
-    if (o.uploaded) {
-      std::string text;
-      dump_json(*exprs->get(o.var)->get("pushDown"), text);
-      evaluate(E, text, pp.data(), pp.size(), glob_size, LK_MERGED, nullptr, false, o.res.get());
-      lk_result& r = *o.res;
-      if (r.exemplar) refuse("expression " + o.var + ": rows with per-row tags");
-      if (r.nrows) {
-        const size_t n = r.nrows;
-        HIP_TRY(hipMalloc(&r.dev_rows, n * 20 + 64));
-        uint8_t* d = static_cast<uint8_t*>(r.dev_rows);
-        HIP_TRY(hipMemcpy(d, r.ts, n * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d + n * 8, r.val, n * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d + n * 16, r.gid, n * 4, hipMemcpyHostToDevice));
-        o.ts_lo = r.ts[0];
-        o.ts_hi = r.ts[n - 1];
+    const int32_t* shard = o.shard.empty() ? nullptr : o.shard.data();
+    auto run = [&] {
+      if (o.uploaded) {
+        std::string text;
+        dump_json(*exprs->get(o.var)->get("pushDown"), text);
+        if (dist) evaluate_comm_held(E, text, pp.data(), pp.size(), glob_size, shard, o.res.get());
+        else evaluate(E, text, pp.data(), pp.size(), glob_size, LK_MERGED, nullptr, false, o.res.get());
+      } else {
+        evaluate_keep_device(E, o.R, pp.data(), pp.size(), glob_size, shard, dist, o.res.get());
       }
-      n_up++;
+    };
+    if (!dist) {
+      run();
     } else {
-      evaluate_keep_device(E, o.R, pp.data(), pp.size(), glob_size, o.res.get());
-      lk_result& r = *o.res;
-      if (r.nrows) {   // rows ascend in time: the first and the last timestamp bound the buckets
-        const int64_t* dts = static_cast<const int64_t*>(r.dev_rows);
-        HIP_TRY(hipMemcpy(&o.ts_lo, dts, 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&o.ts_hi, dts + (r.nrows - 1), 8, hipMemcpyDeviceToHost));
+      // The operand's closing agreement.  Its own collectives fail every rank together; what a rank meets alone behind
+      // the last of them (rank 0 folding the gathered tables, placing the kept rows) is agreed on here, so no rank
+      // starts the next operand's collectives while another unwinds.  Every rank passes the `merge` fault point.
+      int code = 0;
+      std::string msg;
+      try {
+        run();
+        fault_point(E, "merge");
+      } catch (const PlanError& e) {
+        code = e.code, msg = e.what();
+      } catch (const JsonError& e) {
+        code = LK_ERR_ARG, msg = e.what();
+      } catch (const std::bad_alloc&) {
+        code = LK_ERR_MEMORY, msg = "out of host memory";
+      } catch (const std::exception& e) {
+        code = LK_ERR_DEVICE, msg = e.what();
       }
-      n_dev++;
+      CtxLease X(E);
+      X->pend_code = 0;
+      X->pend_msg.clear();
+      comm_agree(E, *X, code, msg.empty() ? std::string() : "formula: expression " + o.var + ": " + msg);
     }
+    (o.uploaded ? n_up : n_dev)++;
+    std::string reduce = "none";
     if (!o.res->stats.empty()) {
       try {
         Json st = Json::parse(o.res->stats);
         if (const Json* x = st.get("rows_scanned")) rows_scanned += (unsigned long long)x->as_i64();
         if (const Json* x = st.get("scan_ms")) scan_ms += x->num;
+        if (const Json* x = st.get("reduce"); x && x->is_str()) reduce = x->str;
       } catch (const JsonError&) {
       }
     }
-    if (o.res->nrows > 0xffffffffull) refuse("expression " + o.var + " has 2^32 rows or more");
+    op_stats += std::string(op_stats.empty() ? "" : ",") + "{\"var\":\"" + json_escape(o.var) + "\",\"reduce\":\"" + json_escape(reduce) +
+                "\",\"rows\":" + std::to_string(o.res->nrows) + ",\"kept\":" + (o.uploaded ? "false" : "true") + "}";
+  }
+  const std::string fx_tail = ",\"world\":" + std::to_string(world) + ",\"rank\":" + std::to_string(rank) + ",\"operands\":[" + op_stats + "]}}";
+  // Behind the last operand's last collective: from here a failure unwinds this rank alone.  The other ranks return
+  // their empty result; rank 0 looks at the rows for the first time.
+  if (rank != 0) {
+    res->exemplar = true;
+    char b0[384];
+    snprintf(b0, sizeof(b0),
+             "{\"scan_ms\":%.6f,\"total_ms\":%.6f,\"rows_scanned\":%llu,\"cells\":0,\"operand_rows\":0,\"formula\":{\"mode\":\"dense\","
+             "\"cells\":0,\"operands_on_device\":%zu,\"operands_uploaded\":%zu,\"regrows\":0",
+             scan_ms, ms_since(t_start), rows_scanned, n_dev, n_up);
+    res->stats = b0 + fx_tail;
+    return LK_OK;
+  }
+  HIP_TRY(hipSetDevice(E.device));
+  for (Operand& o : ops) {
+    lk_result& r = *o.res;
+    if (r.exemplar) refuse("expression " + o.var + ": rows with per-row tags");
+    if (r.nrows > 0xffffffffull) refuse("expression " + o.var + " has 2^32 rows or more");
+    if (!r.nrows) continue;
+    const size_t n = r.nrows;
+    if (o.uploaded) {
+      HIP_TRY(hipMalloc(&r.dev_rows, n * 20 + 64));
+      uint8_t* d = static_cast<uint8_t*>(r.dev_rows);
+      HIP_TRY(hipMemcpy(d, r.ts, n * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(d + n * 8, r.val, n * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(d + n * 16, r.gid, n * 4, hipMemcpyHostToDevice));
+      o.ts_lo = r.ts[0];
+      o.ts_hi = r.ts[n - 1];
+    } else {   // rows ascend in time: the first and the last timestamp bound the buckets
+      const int64_t* dts = static_cast<const int64_t*>(r.dev_rows);
+      HIP_TRY(hipMemcpy(&o.ts_lo, dts, 8, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&o.ts_hi, dts + (n - 1), 8, hipMemcpyDeviceToHost));
+    }
   }
   const double operands_ms = ms_since(t_start);
 
@@ -305,10 +382,10 @@ int evaluate_formula(Engine& E, const std::string& json, int glob_size, lk_resul
              "{\"scan_ms\":%.6f,\"total_ms\":%.6f,\"rows_scanned\":%llu,\"cells\":%llu,\"operand_rows\":%zu,"
              "\"operands_ms\":%.6f,\"scatter_ms\":%.6f,\"eval_ms\":%.6f,\"transfer_ms\":%.6f,\"link_bytes\":%zu,"
              "\"formula\":{\"mode\":\"%s\",\"cells\":%llu,\"operands_on_device\":%zu,\"operands_uploaded\":%zu,"
-             "\"regrows\":%d}}",
+             "\"regrows\":%d",
              scan_ms, ms_since(t_start), rows_scanned, cells, total_rows, operands_ms, scatter_ms, eval_ms, transfer_ms,
              out_rows * 24, mode, cells, n_dev, n_up, regrows);
-    res->stats = buf;
+    res->stats = buf + fx_tail;
   };
   if (!total_rows) {
     write_stats("dense", 0, 0, 0, 0, 0, 0);

@@ -295,6 +295,20 @@ class Engine:
                                       ctypes.byref(h)))
         return Result(h)
 
+    def eval_formula_dist(self, formula: str, expressions: Dict[str, dict], glob_size: int = 10) -> Result:
+        """lk_eval_formula_dist: eval_formula with a rank per pod.  An expression may carry "shard": one rank per path
+        (absent: i % world).  Rank 0 gets the formula's rows, every other rank an empty result with stats."""
+        ex = {}
+        for name, e in expressions.items():
+            pd = e["pushDown"]
+            ex[name] = {"pushDown": json.loads(pd) if isinstance(pd, str) else pd, "paths": list(e["paths"])}
+            if e.get("shard") is not None:
+                ex[name]["shard"] = [int(r) for r in e["shard"]]
+        h = ctypes.c_void_p()
+        check(_lib.lib().lk_eval_formula_dist(self._h, json.dumps({"formula": formula, "expressions": ex}).encode(),
+                                              glob_size, ctypes.byref(h)))
+        return Result(h)
+
 
 def evaluate_push_down_request(engine: Engine, query_id: str, local_parquet: bool, push_down_request: str,
                                paths: Sequence[str]) -> List[List[Row]]:

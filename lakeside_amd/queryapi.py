@@ -221,12 +221,16 @@ def formula_label(formula: str, base_expressions: Dict[str, dict], tags: Dict[st
 
 def evaluate_formula(engine, base_expressions: Dict[str, dict], formula: str,
                      segment_requests_by_id: Dict[str, Sequence[dict]], paths_by_id: Dict[str, Sequence[str]],
-                     step_ms: int, glob_size: int = 10, now_ms: Optional[int] = None) -> List[dict]:
+                     step_ms: int, glob_size: int = 10, now_ms: Optional[int] = None, distributed: bool = False,
+                     shard_by_id: Optional[Dict[str, Sequence[int]]] = None) -> List[dict]:
     """QueryEngineV2.evaluateFormula (QueryEngineV2.scala:310-389) for one SegmentGroup, then toGenericSSEPayload
     (400-417) with id = the formula text (387): one lk_eval_formula call -- the base expressions are evaluated and
     joined per (timestamp, group key) on the device, only the combined rows come back -- then the future-timestamp
     drop (TimeGroupedSketchAggregator.scala:200-222; the leaf and the formula pass both drop per timestamp, so
-    dropping last is the same) and the payloads.  Payloads of one timestamp come out in key order."""
+    dropping last is the same) and the payloads.  Payloads of one timestamp come out in key order.
+    distributed: one lk_eval_formula_dist call, every rank of the engine's communicator making it with the same
+    arguments; `shard_by_id[name]` gives the rank of every path of that expression (absent: i % world).  Rank 0 returns
+    the payloads, every other rank []."""
     now = int(time.time() * 1000) if now_ms is None else int(now_ms)
     for be in base_expressions.values():   # the engine applies the leaves' transformers: same step, checked here
         transformer(be, step_ms)
@@ -235,7 +239,9 @@ def evaluate_formula(engine, base_expressions: Dict[str, dict], formula: str,
         exprs[name] = {"pushDown": {"baseExpr": be, "segmentRequests": list(segment_requests_by_id[name]),
                                     "reverseSort": False, "isTagQuery": False},
                        "paths": list(paths_by_id[name])}
-    res = engine.eval_formula(formula, exprs, glob_size)
+        if distributed and shard_by_id and shard_by_id.get(name) is not None:
+            exprs[name]["shard"] = list(shard_by_id[name])
+    res = engine.eval_formula_dist(formula, exprs, glob_size) if distributed else engine.eval_formula(formula, exprs, glob_size)
     gbs = sorted({g for be in base_expressions.values() for g in ((be.get("chart") or {}).get("groupBys") or [])})
     rows = [(int(t), tuple(tg.get(g, "") for g in gbs), float(v), tg)
             for t, v, tg in zip(res.ts, res.values, res.tags) if int(t) <= now]
