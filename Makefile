@@ -18,8 +18,8 @@ HOST_OBJS = $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(HOST_SRCS))
 # the fused scan kernels: one unit per (aggregate, kernel family, table mode) so they compile in parallel
 SCAN_LEAN  = $(foreach a,sum min max count,$(foreach m,d h,$(OBJDIR)/scan_$(a)_lean_$(m).o))
 SCAN_TILES = $(foreach a,sum min max count,$(foreach m,d h,$(OBJDIR)/scan_$(a)_tiles_$(m).o))
-# scan_clu (the name-clustered value copy): SUM / MIN / MAX, dense tables only
-SCAN_CLU   = $(foreach a,sum min max,$(OBJDIR)/scan_$(a)_clu_d.o)
+# scan_clu (the name-clustered value copy): SUM / MIN / MAX / COUNT (AVG scans as SUM), dense tables only
+SCAN_CLU   = $(foreach a,sum min max count,$(OBJDIR)/scan_$(a)_clu_d.o)
 HIP_OBJS  = $(OBJDIR)/kernels.o $(OBJDIR)/ex_kernels.o $(OBJDIR)/formula_kernels.o $(OBJDIR)/clu_kernels.o $(SCAN_LEAN) $(SCAN_TILES) $(SCAN_CLU)
 HDRS = $(wildcard $(SRC)/*.hpp) $(SRC)/unicode_tables.inc include/lakeside_gpu.h include/lakeside_regex.h include/lakeside_text.h
 # device code includes only these (host-only header edits do not rebuild the kernels); lean_kernel.hpp only the
@@ -30,6 +30,7 @@ DEV_HDRS = $(SRC)/device_common.hpp $(SRC)/kernels.hpp $(SRC)/layout.hpp $(SRC)/
 $(OBJDIR)/formula_kernels.o: HIPFLAGS += -ffp-contract=off
 $(OBJDIR)/formula_kernels.o: $(SRC)/formula_cell.hpp $(SRC)/formula_kernels.hpp
 
+.DEFAULT_GOAL := all
 all: $(LIB) $(SYNTH) $(RELIB) $(TXLIB)
 
 $(OBJDIR)/%.o: $(SRC)/%.cpp $(HDRS)

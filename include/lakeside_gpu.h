@@ -62,8 +62,10 @@ enum {
  * process's OMP_NUM_THREADS share of the host's cores, at most 16.
  * cluster_values: a load also keeps, per tile, a copy of `_cardinalhq.value` grouped by `_cardinalhq.name` code (10 B
  * per row of eligible tiles and 32 B of aggregates per (tile, name code), counted in the cache weight), which
- * name-filtered SUM / MIN / MAX queries stream -- or, for tiles inside one time bucket, merge from the aggregates --
- * instead of gathering values row by row; false = no copy, for deployments that prefer the cache capacity.
+ * name-filtered SUM / MIN / MAX / AVG queries stream -- or, for tiles inside one time bucket, merge from the aggregates
+ * -- instead of gathering values row by row, and from whose per-code element ranges name-filtered COUNT queries take
+ * their counts without reading a value (AVG is the sum with those counts); false = no copy, for deployments that prefer
+ * the cache capacity.
  * Replaces DuckDbConnectionFactory (core/.../utils/DuckDbConnectionFactory.scala:76-114). */
 int lk_engine_create(const char* options_json, lk_engine** out);
 void lk_engine_destroy(lk_engine* e);

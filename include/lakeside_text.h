@@ -75,6 +75,15 @@ uint32_t lk_clu_sub_bytes(uint32_t nrows, uint32_t dict_n, uint32_t c, uint32_t 
  * nrows rows with boundary rows sb[0 .. nsb) (ascending; sb[k] = the first row of class k + 1; nsb <= 4), cls[j] = the
  * class of every row of sub-block j, or 0xffffffff when the sub-block's rows must be streamed.  Returns the sub-blocks. */
 uint32_t lk_clu_sub_sim(uint32_t nrows, const uint32_t* sb, uint32_t nsb, uint32_t* cls);
+/* COUNT over a split tile needs no value (clu.hpp, clu_count_split, the arithmetic of scan_clu<AGG_COUNT>): the
+ * per-class counts of one code of a tile of nrows rows (<= 65,536), given the rows within the tile of its n elements
+ * (rows[0 .. n), strictly ascending: the code's crows) and the boundary rows sb[0 .. nsb) (ascending, nsb <= 4).  The
+ * code's csub entries are built from the rows here.  use_sub != 0: whole sub-blocks add their csub difference to
+ * their class and only the straddling ones' elements are classed one by one; 0: every element is.  cnt[0 .. 4] = the
+ * elements of class 0 .. 4 (class k = k boundaries at or below the row; scan_clu merges classes 1 .. nsb - 1).
+ * Returns 5, or -1 for arguments outside these bounds. */
+int lk_clu_count_sim(uint32_t nrows, const uint16_t* rows, uint32_t n, const uint32_t* sb, uint32_t nsb, int use_sub,
+                     uint32_t* cnt);
 
 /* Plans the filter of a PushDownRequest as the evaluator does before it reads a segment (lakeside_amd/csrc/
  * filter_plan.cpp: the leaf loop of the shape gate, plan_filter, plan_truth); numeric_group_bys[0..n) are the groupBys

@@ -64,6 +64,54 @@ LK_BK_HD inline uint32_t clu_sub_class(uint32_t j, uint32_t nrows, const uint32_
   return whole ? c : CLU_SUB_STRADDLE;
 }
 
+// COUNT over a split tile (scan_clu<AGG_COUNT>, clu_kernel.hpp) needs no value: the per-class counts of one code, stated
+// here once and pinned on the CPU (tests/test_clu_count_cpu.py through clu_sim.cpp, lk_clu_count_sim).
+//
+// A row's class: the number of boundary rows at or below it.  sb holds CLU_SPLIT_MAX entries, those past the tile's
+// nsb boundaries set to ~0 (no row reaches them).
+LK_BK_HD inline uint32_t clu_split_class(uint32_t r, const uint32_t* sb) {
+  uint32_t c = 0u;
+  for (uint32_t k = 0; k < CLU_SPLIT_MAX; k++) c += r >= sb[k] ? 1u : 0u;
+  return c;
+}
+// A code's elements [a, b) of one sub-block (two neighbouring csub entries) clamped to the code's range [s, e) of the
+// tile, as cpref is clamped to the tile's rows: s <= a <= b <= e afterwards.
+LK_BK_HD inline void clu_sub_clamp(uint32_t& a, uint32_t& b, uint32_t s, uint32_t e) {
+  b = b < e ? b : e;
+  b = b > s ? b : s;
+  a = a > s ? a : s;
+  a = a < b ? a : b;
+}
+// One code of a split tile of nrows rows: its elements [s, e) of the tile, rows[i] the row within the tile of element
+// s + i (ascending: crows + s), csub[0 .. clu_nsub(nrows)] its entries of the sub-block area (element indices within
+// the tile; read only when use_sub), the boundary rows sb[0 .. nsb).  cnt[0 .. CLU_SPLIT_MAX] += the elements of each
+// class (scan_clu merges the in-window classes 1 .. nsb - 1 and drops class 0 and class nsb).  With the area a whole
+// sub-block (clu_sub_class) adds b - a to its class without looking at a row, the elements of a straddling one are
+// classed one by one; without it every element is.  scan_clu<AGG_COUNT> mirrors this line for line: lane j is the
+// iteration j of the sub-block loop, the element loops are spread over the wave's lanes.
+LK_BK_HD inline void clu_count_split(const uint16_t* rows, uint32_t s, uint32_t e, const uint32_t* csub, uint32_t nrows,
+                                     const uint32_t* sb, uint32_t nsb, bool use_sub, uint32_t* cnt) {
+  uint32_t sbp[CLU_SPLIT_MAX];
+  for (uint32_t k = 0; k < CLU_SPLIT_MAX; k++) sbp[k] = k < nsb ? sb[k] : 0xffffffffu;
+  if (s >= e) return;
+  if (!use_sub) {
+    for (uint32_t i = s; i < e; i++) cnt[clu_split_class(uint32_t(rows[i - s]), sbp)] += 1u;
+    return;
+  }
+  const uint32_t nsub = clu_nsub(nrows);
+  for (uint32_t j = 0; j < nsub; j++) {
+    uint32_t a = csub[j], b = csub[j + 1u];
+    clu_sub_clamp(a, b, s, e);
+    if (a >= b) continue;
+    const uint32_t subc = clu_sub_class(j, nrows, sbp, nsb);
+    if (subc != CLU_SUB_STRADDLE) {
+      cnt[subc] += b - a;
+      continue;
+    }
+    for (uint32_t i = a; i < b; i++) cnt[clu_split_class(uint32_t(rows[i - s]), sbp)] += 1u;
+  }
+}
+
 enum CluKind : uint32_t {
   CLU_NONE = 0,     // outside the glob window: no row of the tile counts
   CLU_PINNED,       // every row in bucket b0

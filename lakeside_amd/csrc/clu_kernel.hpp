@@ -1,7 +1,13 @@
-// scan_clu<AGG> (SUM, MIN, MAX; dense tables): the name-filter scan over the name-clustered value copy (layout.hpp,
-// CluTile; built at load by clu_build, clu_kernels.hip).  Included by the scan_<agg>_clu_d.hip units through
-// scan_inst.hpp.  The host (eval_plan.cpp, plan_cluster) hands it the segments whose every tile clu_tile takes, so
-// neither scan_lean nor scan_tiles runs over them.
+// scan_clu<AGG> (SUM, MIN, MAX, COUNT; dense tables): the name-filter scan over the name-clustered value copy
+// (layout.hpp, CluTile; built at load by clu_build, clu_kernels.hip).  Included by the scan_<agg>_clu_d.hip units
+// through scan_inst.hpp.  The host (eval_plan.cpp, plan_cluster) hands it the segments whose every tile clu_tile takes,
+// so neither scan_lean nor scan_tiles runs over them.  An AVG chart arrives as AGG_SUM with the table's `rows` plane
+// kept (setup_scan: LEAN_NO_CNT without LEAN_SUM_EXISTS): global_merge adds the element counts the SUM paths pass.
+//
+// COUNT reads no value at all (its code is guarded with `if constexpr`; the other instantiations compile to what they
+// were): a pinned tile's count of code c is cpref[c + 1] - cpref[c], whatever LK_NO_CLU_AGG says; of a split tile, a
+// whole sub-block's is csub[c][j + 1] - csub[c][j] and only a straddling sub-block's crows (2 B per element) are
+// streamed and classed -- clu.hpp's clu_count_split, mirrored line for line.  No cvals, cagg, sagg or NaN mask.
 //
 // Per tile: the passing-code mask exactly as scan_lean computes it (remap -> strtab -> T / F bits -> truth word,
 // leaf_false included).  A pinned tile's elements all land in one bucket, and what its passing codes contribute --
@@ -43,7 +49,7 @@ typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 
 template <int AGG>
 __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
-  static_assert(AGG == AGG_SUM || AGG == AGG_MIN || AGG == AGG_MAX, "scan_clu: SUM, MIN, MAX");
+  static_assert(AGG == AGG_SUM || AGG == AGG_MIN || AGG == AGG_MAX || AGG == AGG_COUNT, "scan_clu: SUM, MIN, MAX, COUNT");
   const uint32_t lane = threadIdx.x & 63u;
   const QSeg* Sp = P.segs + blockIdx.y;
   const uint32_t t = uni(blockIdx.x * uint32_t(CLU_WAVES) + (threadIdx.x >> 6));
@@ -63,8 +69,9 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
   const bool count_plan = P.plan_bytes != nullptr;
   uint64_t pbytes = 0;
   const uint8_t* blk = Sp->clu_base + d.off;
-  // a pinned tile merges the copy's per-code aggregates (LK_NO_CLU_AGG=1: it streams the ranges, as a split tile must)
-  const bool use_agg = cc.kind == CLU_PINNED && !(P.split_ok & SPLIT_OK_NO_CLU_AGG) && d.nrows <= tdp->nrows;   // uniform
+  // a pinned tile merges the copy's per-code aggregates (LK_NO_CLU_AGG=1: it streams the ranges, as a split tile must;
+  // COUNT has nothing to stream: a pinned tile's counts are cpref's differences whatever the switch says)
+  const bool use_agg = AGG != AGG_COUNT && cc.kind == CLU_PINNED && !(P.split_ok & SPLIT_OK_NO_CLU_AGG) && d.nrows <= tdp->nrows;   // uniform
 
   // lane c: the code's range [cs, ce) of cvals / crows and, for a pinned tile, its aggregate.  Loaded for every code
   // beside the remap entry, before the truth word says which codes pass: the three depend on CluTile / TileCol alone,
@@ -113,6 +120,16 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
   const uint32_t stride = P.strp[0].dim_stride;
   const unsigned long long glob_base = (unsigned long long)Sp->glob_slot * P.nbuckets;
 
+  if constexpr (AGG == AGG_COUNT) {
+    if (cc.kind == CLU_PINNED) {   // uniform: lane c's count is its code's clamped range, no further line is read
+      if (pass && cs < ce) {
+        const unsigned long long cell = (glob_base + (unsigned long long)cc.b0) * P.ngroups + (lut & DIM_MASK) * stride;
+        global_merge<AGG_COUNT, false>(P, cell, ce - cs, ce - cs, 0.0, 0.0, 0ull);
+      }
+      if (pbytes) atomicAdd(P.plan_bytes, (unsigned long long)pbytes);
+      return;
+    }
+  }
   if (use_agg) {   // uniform: every passing lane merges its own code (codes sharing a dim meet in the atomics)
     if (pass && cs < ce) {
       const unsigned long long cell = (glob_base + (unsigned long long)cc.b0) * P.ngroups + (lut & DIM_MASK) * stride;
@@ -195,6 +212,90 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
     for (uint32_t k = 0; k < CLU_SPLIT_MAX; k++) c += r >= sb[k] ? 1u : 0u;
     return c;
   };
+
+  // COUNT of a split tile (pinned ones ended above): clu_count_split (clu.hpp) mirrored line for line -- lane j is its
+  // sub-block iteration j, its element loops are spread over the wave -- with the shared clu_sub_class, clu_sub_clamp
+  // and clu_split_class.  No value, aggregate or NaN bit is read: with the area, lane j loads the code's csub[c][j] and
+  // csub[c][j + 1], a whole sub-block of an in-window class adds b - a, and only the straddling sub-blocks' crows are
+  // streamed; without it (LK_NO_CLU_SUB=1, or no area) the code's whole crows range is.  crows: one 2-B load per lane
+  // per step, eight steps in flight, as the SUM path loads them.  Counts are exact uint32 (a tile has <= 65,536 rows).
+  if constexpr (AGG == AGG_COUNT) {
+    const bool use_sub = Sp->clu_sub != nullptr && !(P.split_ok & SPLIT_OK_NO_CLU_SUB) && d.nrows <= tdp->nrows &&
+                         clu_sub_bytes(d.dict_n) <= Sp->clu_sub_stride && dict_n <= clu_dict_n(d.dict_n);   // uniform
+    const __amdgpu_buffer_rsrc_t rsub =
+        make_rsrc(use_sub ? Sp->clu_sub + uint64_t(t) * Sp->clu_sub_stride : nullptr, use_sub ? clu_sub_bytes(d.dict_n) : 0u);
+    const uint32_t nsub = clu_nsub(nrows);
+    uint32_t subc = CLU_SUB_STRADDLE;
+    if (use_sub && lane < nsub) subc = clu_sub_class(lane, nrows, sb, nsb);
+    constexpr uint32_t NK = CLU_SPLIT_MAX - 1u;   // the in-window classes 1 .. nsb - 1
+    while (emask) {
+      const uint32_t c = uint32_t(__builtin_ctzll(emask));
+      emask &= emask - 1ull;
+      const uint32_t s = uni(__shfl(cs, int(c), 64)), e = uni(__shfl(ce, int(c), 64));
+      if (s >= e) continue;   // the name is absent from the tile
+      const uint32_t dim = (uni(__shfl(lut, int(c), 64)) & DIM_MASK) * stride;
+      uint32_t cnt[NK];
+#pragma unroll
+      for (uint32_t k = 0; k < NK; k++) cnt[k] = 0u;
+      // the elements [s0, s0 + n) of crows into the counters (s <= s0, s0 + n <= e <= nrows: inside the tile's crows)
+      auto count_rows = [&](uint32_t s0, uint32_t n) __attribute__((always_inline)) {
+        constexpr uint32_t U = 8u;
+        for (uint32_t i0 = 0; i0 < n; i0 += 64u * U) {
+          uint32_t r[U];
+#pragma unroll
+          for (uint32_t u = 0; u < U; u++) {
+            const uint32_t i = i0 + 64u * u + lane;
+            r[u] = i < n ? uint32_t(crows[s0 + i]) : 0u;
+          }
+#pragma unroll
+          for (uint32_t u = 0; u < U; u++) {
+            const bool live = i0 + 64u * u + lane < n;
+            const uint32_t cl = clu_split_class(r[u], sb);
+#pragma unroll
+            for (uint32_t k = 0; k < NK; k++) cnt[k] += live && cl == k + 1u && k + 1u < nsb ? 1u : 0u;
+          }
+        }
+        if (count_plan && lane == 0)   // the 128-B lines of the streamed row indices
+          pbytes += 128u * uint64_t((((s0 + n) * 2u + 127u) >> 7) - ((s0 * 2u) >> 7));
+      };
+      if (!use_sub) {   // uniform
+        count_rows(s, e - s);
+      } else {
+        const bool sl = lane < nsub;
+        const uint32_t co = clu_sub_csub_off(d.dict_n) + c * (CLU_SUB_MAX + 1u) * 4u;
+        uint32_t a = __builtin_amdgcn_raw_buffer_load_b32(rsub, sl ? lane * 4u : OOB, int(co), 0);
+        uint32_t b = __builtin_amdgcn_raw_buffer_load_b32(rsub, sl ? lane * 4u + 4u : OOB, int(co), 0);
+        if (!sl) a = b = e;
+        clu_sub_clamp(a, b, s, e);
+        if (subc != CLU_SUB_STRADDLE && subc >= 1u && subc < nsb && a < b) {
+#pragma unroll
+          for (uint32_t k = 0; k < NK; k++)
+            if (subc == k + 1u) cnt[k] = b - a;
+        }
+        // at most CLU_SPLIT_MAX - 1 sub-blocks hold a boundary inside the tile
+        unsigned long long strad = __ballot(sl && subc == CLU_SUB_STRADDLE && a < b);
+        while (strad) {   // uniform
+          const int j = __builtin_ctzll(strad);
+          strad &= strad - 1ull;
+          const uint32_t qa = uni(__shfl(a, j, 64)), qb = uni(__shfl(b, j, 64));
+          count_rows(qa, qb - qa);
+        }
+        if (count_plan && lane == 0)   // the 128-B lines of the csub entries read
+          pbytes += 128u * uint64_t(((co + (nsub + 1u) * 4u + 127u) >> 7) - (co >> 7));
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < NK; k++) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) cnt[k] += __shfl_xor(cnt[k], off, 64);
+        if (lane == 0 && cnt[k]) {
+          const unsigned long long cell = (glob_base + (unsigned long long)(cc.b0 + int64_t(k))) * P.ngroups + dim;
+          global_merge<AGG_COUNT, false>(P, cell, cnt[k], cnt[k], 0.0, 0.0, 0ull);
+        }
+      }
+    }
+    if (pbytes) atomicAdd(P.plan_bytes, (unsigned long long)pbytes);
+    return;
+  }
 
   bool nan_seen = false;
 

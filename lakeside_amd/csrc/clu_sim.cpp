@@ -42,6 +42,25 @@ extern "C" uint32_t lk_clu_sub_sim(uint32_t nrows, const uint32_t* sb, uint32_t 
   return n;
 }
 
+extern "C" int lk_clu_count_sim(uint32_t nrows, const uint16_t* rows, uint32_t n, const uint32_t* sb, uint32_t nsb,
+                                int use_sub, uint32_t* cnt) {
+  using namespace lk;
+  if (nrows == 0 || nrows > TILE_ROWS || n > nrows || nsb > CLU_SPLIT_MAX) return -1;
+  for (uint32_t i = 0; i < n; i++)
+    if (rows[i] >= nrows || (i && rows[i] <= rows[i - 1])) return -1;
+  // the code's elements lie at [s, s + n) of the tile, other codes' before and after; csub as clu_build writes it
+  const uint32_t s = (nrows - n) / 2u, e = s + n;
+  uint32_t csub[CLU_SUB_MAX + 1u];
+  uint32_t i = 0;
+  for (uint32_t j = 0; j <= CLU_SUB_MAX; j++) {
+    while (i < n && uint32_t(rows[i]) < CLU_SUB_ROWS * j) i++;
+    csub[j] = s + i;   // past the tile's sub-blocks: e
+  }
+  for (uint32_t k = 0; k <= CLU_SPLIT_MAX; k++) cnt[k] = 0u;
+  clu_count_split(rows, s, e, csub, nrows, sb, nsb, use_sub != 0, cnt);
+  return int(CLU_SPLIT_MAX + 1u);
+}
+
 extern "C" int lk_clu_segment_taken(int all_copies_sorted, int64_t widest, int64_t step) {
   return lk::clu_segment_taken(all_copies_sorted != 0, widest, step) ? 1 : 0;
 }

@@ -815,12 +815,14 @@ void plan_segments(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp
   // row scan (ex_scan AGG mode): every segment of a numeric-leaf query, and segments whose timestamp or value column
   // needs union_by_name promotion (INT32 timestamps; INT32 / INT64 / FLOAT values, cast through FLOAT where the glob's
   // value type is FLOAT).  Both kinds aggregate into the same table.
-  // scan_clu's query shape (clu_kernel.hpp): one string column, the name, filtered through a truth table; SUM, MIN or
-  // MAX of `_cardinalhq.value` with no value leaf, sketch or cardinality estimate; buckets on the step grid.
+  // scan_clu's query shape (clu_kernel.hpp): one string column, the name, filtered through a truth table; SUM, MIN,
+  // MAX, COUNT or AVG (scanned as SUM with the row counts, setup_scan) of `_cardinalhq.value` with no value leaf, sketch
+  // or cardinality estimate; buckets on the step grid.
   // LK_NO_CLUSTER=1 (read per call: A/B) sends every segment down the other kernels, as do the switches that turn
   // off the machinery it relies on.
   const bool clu_query = fp.cols.size() == 1 && !qs.tagq && fp.cols[0].name == kName && !fp.truth.empty() &&
-                         (qs.agg == AGG_SUM || qs.agg == AGG_MIN || qs.agg == AGG_MAX) && !qs.sketch && !qs.ces &&
+                         (qs.agg == AGG_SUM || qs.agg == AGG_MIN || qs.agg == AGG_MAX || qs.agg == AGG_COUNT ||
+                          qs.agg == AGG_AVG) && !qs.sketch && !qs.ces &&
                          !qs.numeric && !fp.vleaf && qs.nums.empty() && qs.numgbs.empty() && !qs.metrics && !qs.fchart &&
                          !qs.no_value_col && qs.vcol == kValue && gp.step > 0 && !getenv("LK_NO_CLUSTER") &&
                          !getenv("LK_NO_LEAN_SPLIT") && !getenv("LK_NO_SPLIT");

@@ -788,6 +788,7 @@ hipError_t launch_scan_clu(const QParams& P, int agg, hipStream_t stream) {
     case AGG_SUM: launch_clu<AGG_SUM>(P, grid, stream); break;
     case AGG_MIN: launch_clu<AGG_MIN>(P, grid, stream); break;
     case AGG_MAX: launch_clu<AGG_MAX>(P, grid, stream); break;
+    case AGG_COUNT: launch_clu<AGG_COUNT>(P, grid, stream); break;
     default: return hipErrorInvalidValue;   // no quiet fall-back: the host asks only for these
   }
   return hipGetLastError();

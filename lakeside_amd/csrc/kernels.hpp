@@ -244,7 +244,8 @@ hipError_t launch_merge_tables(const TableRef& T, const unsigned long long* part
                                hipStream_t stream);
 hipError_t launch_scan(const QParams& P, int agg, hipStream_t stream);
 // scan_clu (clu_kernel.hpp) over P.segs[0 .. nsegs): segments that carry the name-clustered value copy and whose every
-// tile it takes (QSeg::clu set); agg is AGG_SUM, AGG_MIN or AGG_MAX, the table dense
+// tile it takes (QSeg::clu set); agg is AGG_SUM (AVG charts too: the kernels' aggregate), AGG_MIN, AGG_MAX or AGG_COUNT
+// (which reads no value: cpref / csub differences and the straddling sub-blocks' row indices), the table dense
 hipError_t launch_scan_clu(const QParams& P, int agg, hipStream_t stream);
 // clu_build (clu_kernels.hip): the clustered copy of every tile of one segment whose descriptor has a block
 struct CluBuild {
