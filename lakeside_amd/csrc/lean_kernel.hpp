@@ -808,6 +808,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LeanShape
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         pc[j] = em ? uint32_t(__builtin_ctzll(em)) : 0xffffffffu;
+        // a passing code the page's BW-bit fields cannot hold (a page written while the chunk dictionary was still
+        // small): no row of the tile has it, and pc * REP would spill into the neighbouring fields and match other
+        // codes.  The codes ascend, so every later one is dropped with it.
+        if (POW2 && pc[j] >= (1u << BW)) pc[j] = 0xffffffffu;
         em &= em ? em - 1 : 0ull;
       }
     }

@@ -3,7 +3,7 @@
 // a GPU (`make sanitize`; VERDICT r4 next #8 -- the use-after-free of eebca43 was a ChunkOut stream pointing into a
 // reallocated buffer, which ASan reports here).
 //
-//   load_check <threads> <file.parquet>...
+//   load_check [--tiles] <threads> <file.parquet>...
 //
 // Loads every file in order into one set of engine dictionaries (as one engine would), stages each segment's stream
 // area in three pieces (the piece boundaries of the upload path), and prints a digest per segment: rows, columns,
@@ -11,6 +11,12 @@
 // finally every dictionary's size and a hash of its values in id order.  The digest must not depend on the thread
 // count (tests/test_load_check.py compares 1 and 8 threads).  A file that fails to load prints its error and the
 // harness goes on (corrupt-file fixtures).
+//
+// --tiles: after each segment's digest, one line per tile for the `_cardinalhq.name` column -- what the name-clustered
+// value copy's builder (Engine::build_cluster) and the scan kernels see of it: the tile's rows, TILE_TS_SORTED and
+// ts_max - ts_min, the page kind, chunk dictionary size and index width, the first value index, the run count, and the
+// first run's start and kind.  tests/test_clu_shapes_cpu.py pins its fixtures' shapes with it.  Without the flag the
+// output is what it was.
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -36,8 +42,14 @@ constexpr uint64_t kFnv0 = 1469598103934665603ull;
 }  // namespace
 
 int main(int argc, char** argv) {
+  bool show_tiles = false;
+  if (argc > 1 && !strcmp(argv[1], "--tiles")) {
+    show_tiles = true;
+    argv++;
+    argc--;
+  }
   if (argc < 3) {
-    fprintf(stderr, "usage: load_check <threads> <file.parquet>...\n");
+    fprintf(stderr, "usage: load_check [--tiles] <threads> <file.parquet>...\n");
     return 2;
   }
   const int threads = atoi(argv[1]);
@@ -80,6 +92,20 @@ int main(int argc, char** argv) {
         h = fnv(h, c.remap.data(), c.remap.size() * sizeof(uint32_t));
         printf("  col %s type=%d pages=%zu runs=%zu remap=%zu %016llx\n", c.name.c_str(), c.ptype, c.pages.size(),
                c.runs.size(), c.remap.size(), (unsigned long long)h);
+      }
+      const int cn = show_tiles ? S.col_index("_cardinalhq.name") : -1;
+      if (cn >= 0 && S.cols[size_t(cn)].tcols.size() == S.tiles.size()) {
+        const HostCol& N = S.cols[size_t(cn)];
+        for (size_t t = 0; t < S.tiles.size(); t++) {
+          const TileDesc& td = S.tiles[t];
+          const TileCol& tc = N.tcols[t];
+          const bool run0 = tc.nruns > 0 && size_t(tc.run_lo) < N.runs.size();
+          const RunDesc r0 = run0 ? N.runs[tc.run_lo] : RunDesc{0u, 0u, 0u, 0u};
+          printf("  tile %zu rg=%u nrows=%u sorted=%u span=%lld kind=%u dict_n=%u bw=%u vbase=%u nruns=%u has_nulls=%u "
+                 "run0_start=%u run0_lit=%u\n",
+                 t, td.rg, td.nrows, td.pad & TILE_TS_SORTED, (long long)(td.ts_max - td.ts_min), unsigned(tc.kind),
+                 tc.dict_n, unsigned(tc.bw), tc.vbase, tc.nruns, unsigned(tc.has_nulls), r0.start, r0.off_lit >> 31);
+        }
       }
     } catch (const PlanError& e) {
       printf("%s error %d: %s\n", base, e.code, e.what());
