@@ -3,7 +3,7 @@
 // a GPU (`make sanitize`; VERDICT r4 next #8 -- the use-after-free of eebca43 was a ChunkOut stream pointing into a
 // reallocated buffer, which ASan reports here).
 //
-//   load_check [--tiles] <threads> <file.parquet>...
+//   load_check [--tiles[=<column>]] <threads> <file.parquet>...
 //
 // Loads every file in order into one set of engine dictionaries (as one engine would), stages each segment's stream
 // area in three pieces (the piece boundaries of the upload path), and prints a digest per segment: rows, columns,
@@ -16,7 +16,8 @@
 // value copy's builder (Engine::build_cluster) and the scan kernels see of it: the tile's rows, TILE_TS_SORTED and
 // ts_max - ts_min, the page kind, chunk dictionary size and index width, the first value index, the run count, and the
 // first run's start and kind.  tests/test_clu_shapes_cpu.py pins its fixtures' shapes with it.  Without the flag the
-// output is what it was.
+// output is what it was.  --tiles=<column> prints the same lines for another column (tests/test_tag_shapes_cpu.py: the
+// tag column the filter and group-dim decoders read); a segment without that column prints no tile line.
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -43,13 +44,15 @@ constexpr uint64_t kFnv0 = 1469598103934665603ull;
 
 int main(int argc, char** argv) {
   bool show_tiles = false;
-  if (argc > 1 && !strcmp(argv[1], "--tiles")) {
+  std::string tile_col = "_cardinalhq.name";
+  if (argc > 1 && !strncmp(argv[1], "--tiles", 7) && (argv[1][7] == 0 || argv[1][7] == '=')) {
     show_tiles = true;
+    if (argv[1][7] == '=') tile_col = argv[1] + 8;
     argv++;
     argc--;
   }
   if (argc < 3) {
-    fprintf(stderr, "usage: load_check [--tiles] <threads> <file.parquet>...\n");
+    fprintf(stderr, "usage: load_check [--tiles[=<column>]] <threads> <file.parquet>...\n");
     return 2;
   }
   const int threads = atoi(argv[1]);
@@ -93,7 +96,7 @@ int main(int argc, char** argv) {
         printf("  col %s type=%d pages=%zu runs=%zu remap=%zu %016llx\n", c.name.c_str(), c.ptype, c.pages.size(),
                c.runs.size(), c.remap.size(), (unsigned long long)h);
       }
-      const int cn = show_tiles ? S.col_index("_cardinalhq.name") : -1;
+      const int cn = show_tiles ? S.col_index(tile_col) : -1;
       if (cn >= 0 && S.cols[size_t(cn)].tcols.size() == S.tiles.size()) {
         const HostCol& N = S.cols[size_t(cn)];
         for (size_t t = 0; t < S.tiles.size(); t++) {
