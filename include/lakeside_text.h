@@ -34,6 +34,29 @@ int lk_formula_eval_cell(const char* formula, const char* const* names, size_t n
                          const double* value, const int32_t* src, uint8_t* out_present, double* out_value,
                          int32_t* out_src);
 
+/* What lk_eval_formula decides from its request alone, before it evaluates an operand or enters a collective
+ * (lakeside_amd/csrc/formula_join.cpp, fx_gate, with the plain request parser in place of the engine's cache).
+ * formula_json is lk_eval_formula's: {"formula", "expressions": {var: {"pushDown", "paths", "shard"?}}}.  dist = 0: a
+ * local call, "shard" is not read (world is 1); dist != 0: lk_eval_formula_dist among `world` ranks.  Writes into out
+ * (NUL-terminated) {"program": the postfix program as lk_formula_plan prints it, its leaves numbered over the
+ * referenced expressions in the order of "expressions"; "operands": per referenced expression in that order {"var",
+ * "paths", "shard" ([]: i % world), "uploaded" (values assembled on the host), "xform" ("none" / "mul" / "div": the
+ * chart transformer)}; "order": the variables in evaluation order (ascending bytes); "key_cols": the sorted groupBy set;
+ * "step"; "secs"}.  Returns 0, or the refusal's code (LK_ERR_ARG -1, LK_ERR_UNSUPPORTED -2) with its message in out; -5
+ * when cap is too small. */
+int lk_formula_gate_sim(const char* formula_json, int dist, int world, char* out, size_t cap);
+/* The union group space, the collapse ranks and the cell space of a formula's join (formula_join.cpp, fx_union_space
+ * and fx_cell_space) over operands described by their dimension texts.  spec_json: {"key_cols": [groupBy column],
+ * "operands": [null (an expression without rows) | {"name": DIM, "keys": [DIM per key column], "query_tags": [[tag name,
+ * value]] (the first glob's)}], "ident"?: [null | {"ndim", "dict": {text: dictionary id}} per key column],
+ * "cells"?: {"base", "last", "step"}}, DIM = {"tag": the column's tag name, "dims": [text | null (absent) per dim id]}
+ * or, for a column that must not be walked, {"tag", "ndim"}: asking for one of its texts fails the call.  An "ident"
+ * entry makes its column an identity column: union id = dictionary id + 1 for ids below ndim - 1, texts outside them
+ * numbered from ndim + 1 in order of first appearance.  Writes {"U", "ustride", "operands": [{"maps": [[union id per
+ * dim id] per key column, [] for an identity column], "name_rank", "after_name", "qt_ids", "qt_u", "qt_rank"}]} and,
+ * with "cells", "nbuckets" and "nkeys".  Returns as lk_formula_gate_sim does. */
+int lk_formula_union_sim(const char* spec_json, char* out, size_t cap);
+
 /* Runs the exemplar row selection (ex_select.hpp) for one glob over the n passing rows' timestamps ts[0..n), with a
  * CPU histogram standing in for ex_scan HIST: a row counts in a pass iff rlo <= ts < rhi, in bin
  * clamp((ts - hbase) / hwidth, 0, nb - 1).  tiles: ntiles x (ts_min, ts_max, nrows) zone maps for the probes

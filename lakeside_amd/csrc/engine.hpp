@@ -318,6 +318,11 @@ struct lk_result {
   std::deque<std::string> owned;                 // strings not owned by a dictionary
   std::vector<std::shared_ptr<const void>> keep; // dictionary blocks tag pointers point into
   std::string stats;
+  // internal: what formulas and the mixed-step composition read back from an evaluation, set wherever `stats` is
+  // written with these keys (a result whose stats lack a key keeps the default)
+  double scan_ms = 0;
+  unsigned long long rows_scanned = 0;
+  const char* reduce = "none";                   // the distributed reduce path's name (a literal)
   std::vector<std::string> sketches;             // percentile rows: the serialized DDSketch of each row
   // internal (evaluate_mixed_steps): the rows' sketches as objects, so rows of globs with different steps can be
   // merged per (timestamp, tags) as query-api merges sketches (TimeGroupedSketchAggregator.scala:34-43)

@@ -1264,6 +1264,10 @@ void write_rows(const EvalCall& C, const Plan& pl, DevState& dv) {
 }
 
 void write_stats(const EvalCall& C, const Plan& pl, const DevState& dv, const CommCounters& cc0) {
+  const char* reduce = !C.dist ? "none" : (dv.keyrange ? "keyrange" : (pl.cs.hash_mode ? "records_to_root" : "gather_to_root"));
+  C.res->scan_ms = double(dv.scan_ms);
+  C.res->rows_scanned = (unsigned long long)pl.sg.rows_scanned;
+  C.res->reduce = reduce;
   char buf[1280];
   snprintf(buf, sizeof(buf),
            "{\"scan_ms\":%.6f,\"total_ms\":%.6f,\"plan_ms\":%.6f,\"device_ms\":%.6f,\"launch_ms\":%.6f,"
@@ -1275,7 +1279,7 @@ void write_stats(const EvalCall& C, const Plan& pl, const DevState& dv, const Co
            double(dv.scan_ms), ms_since(C.t_start), dv.plan_ms, dv.copy_ms - dv.plan_ms, dv.launch_ms, dv.sync_ms, dv.alloc_ms, dv.copy_ms, (unsigned long long)pl.sg.rows_scanned,
            (unsigned long long)pl.sg.alg_bytes, pl.sg.total_tiles, (unsigned long long)pl.cs.ncells, pl.sg.qsegs.size() + pl.sg.gsegs.size(), pl.sg.gsegs.size(),
            pl.gp.nfailed, pl.cs.hash_mode ? "hash" : "dense", (unsigned long long)(pl.cs.hash_mode ? dv.cap : pl.cs.ncells), dv.nocc, dv.attempts, dv.plan_bytes,
-           !C.dist ? "none" : (dv.keyrange ? "keyrange" : (pl.cs.hash_mode ? "records_to_root" : "gather_to_root")), pl.dp.dims_ms,
+           reduce, pl.dp.dims_ms,
            pl.dp.dims_rebuilt, dv.emit_mode, dv.P.exact_sum, dv.P.global_cells);
   C.res->stats = buf;
   if (C.dist) {   // the distributed call's stages and collectives (this rank)

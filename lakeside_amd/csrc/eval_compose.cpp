@@ -2,7 +2,6 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstring>
 #include <map>
 #include <string>
 #include <tuple>
@@ -103,8 +102,7 @@ int evaluate_mixed_steps(Engine& E, const std::string& json, const Request& R, c
         }
         rows.push_back(std::move(o));
       }
-      const char* k = strstr(r.stats.c_str(), "\"scan_ms\":");
-      if (k) scan_ms += atof(k + 10);
+      scan_ms += r.scan_ms;
     }
   }
   if (!per_glob_rows) {   // query-api merge per (timestamp, tag map), in first-arrival order
@@ -172,6 +170,7 @@ int evaluate_mixed_steps(Engine& E, const std::string& json, const Request& R, c
   snprintf(buf, sizeof buf, "{\"scan_ms\":%.6f,\"total_ms\":%.6f,\"step_groups\":%zu,\"table\":\"per_step\"}", scan_ms,
            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), groups.size());
   res->stats = buf;
+  res->scan_ms = scan_ms;
   return LK_OK;
 }
 
@@ -269,6 +268,9 @@ int evaluate_metrics_pct(Engine& E, const std::string& json, const Request& R, c
   snprintf(buf, sizeof buf, ",\"metrics_pct_rows_in\":%zu,\"pct_total_ms\":%.6f}", r.nrows,
            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   res->stats = st + buf;
+  res->scan_ms = r.scan_ms;
+  res->rows_scanned = r.rows_scanned;
+  res->reduce = r.reduce;
   return LK_OK;
 }
 

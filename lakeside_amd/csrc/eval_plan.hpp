@@ -48,6 +48,16 @@ int evaluate_metrics_pct(Engine& E, const std::string& json, const Request& R, c
 int evaluate_mixed_steps(Engine& E, const std::string& json, const Request& R, const char* const* paths, size_t n_paths,
                          int glob_size, unsigned flags, const int32_t* shard, bool dist, lk_result* res);
 
+// The public evaluation (eval.cpp: metrics percentiles and mixed steps composed, else evaluate_req), and the two
+// operand evaluations of lk_eval_formula (formula_eval.cpp): merged rows kept on the device; a host-assembled operand
+// of a distributed formula, under the comm_mu its caller holds.
+int evaluate(Engine& E, const std::string& json, const char* const* paths, size_t n_paths, int glob_size,
+             unsigned flags, const int32_t* shard, bool dist, lk_result* res);
+int evaluate_keep_device(Engine& E, const std::shared_ptr<const Request>& Rp, const char* const* paths, size_t n_paths,
+                         int glob_size, const int32_t* shard, bool dist, lk_result* res);
+int evaluate_comm_held(Engine& E, const std::string& json, const char* const* paths, size_t n_paths, int glob_size,
+                       const int32_t* shard, lk_result* res);
+
 // The call: its arguments and context, fixed while it runs.
 struct EvalCall {
   Engine& E;

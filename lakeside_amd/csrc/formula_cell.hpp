@@ -27,6 +27,14 @@ constexpr int FX_MAXPROG = 64;    // postfix operations of one formula
 constexpr int FX_MAXLEAF = 8;     // distinct base expressions one formula references
 constexpr int FX_MAXSTACK = 16;   // operand stack (the parser checks the program's depth)
 constexpr int32_t FX_SRC_CONST = -1;
+constexpr int FX_MAXCOL = 8;      // groupBy columns of a formula's key
+// Collapse ranks (smaller wins): a named row 2 * (its name's place in string order) + 4; a row without a name tag
+// sorts before every named row of its key unless one of its present groupBy tags sorts after the name tag; the one
+// all-absent row (queryTags) takes the odd rank between its neighbours (FxOperand::qt_rank).
+constexpr uint32_t FX_RANK_ABSENT = 0xffffffffu;   // name_rank entry of a dim id whose name tag is absent
+constexpr uint32_t FX_RANK_NONAME_FIRST = 1u;
+constexpr uint32_t FX_RANK_NONAME_LAST = 0xfffffffcu;
+enum FxXform : int { FX_XF_NONE = 0, FX_XF_MUL = 1, FX_XF_DIV = 2 };
 
 enum FxOpc : int32_t { FX_LEAF = 0, FX_CONST = 1, FX_ADD = 2, FX_SUB = 3, FX_MUL = 4, FX_DIV = 5 };
 

@@ -21,20 +21,24 @@
 //      joins them with ":");
 //   3. a constant's tags under groupBys are those of the first expression, in the order of `expressions`, that has a
 //      row at that key and timestamp.
+//
+// This file is the stages that need the engine, the communicator or the device; what they decide from the request and
+// from the dimensions' texts alone is formula_join.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/lakeside_gpu.h"
 #include "comm.hpp"
 #include "engine.hpp"
+#include "eval_plan.hpp"
 #include "evalutil.hpp"
 #include "formula.hpp"
+#include "formula_join.hpp"
 #include "formula_kernels.hpp"
 #include "hostutil.hpp"
 #include "json.hpp"
@@ -42,91 +46,182 @@
 
 namespace lk {
 
-int evaluate(Engine& E, const std::string& json, const char* const* paths, size_t n_paths, int glob_size,
-             unsigned flags, const int32_t* shard, bool dist, lk_result* res);
-int evaluate_keep_device(Engine& E, const std::shared_ptr<const Request>& Rp, const char* const* paths, size_t n_paths,
-                         int glob_size, const int32_t* shard, bool dist, lk_result* res);
-int evaluate_comm_held(Engine& E, const std::string& json, const char* const* paths, size_t n_paths, int glob_size,
-                       const int32_t* shard, lk_result* res);
-
 namespace {
 
-void dump_json(const Json& j, std::string& o) {
-  switch (j.kind) {
-    case Json::Null: o += "null"; break;
-    case Json::Bool: o += j.b ? "true" : "false"; break;
-    case Json::Number: o += j.num_text; break;
-    case Json::String: {
-      o += '"';
-      for (char c : j.str) {
-        if (c == '"' || c == '\\') {
-          o += '\\';
-          o += c;
-        } else if (static_cast<unsigned char>(c) < 0x20) {
-          char b[8];
-          snprintf(b, sizeof(b), "\\u%04x", unsigned(static_cast<unsigned char>(c)));
-          o += b;
-        } else {
-          o += c;
-        }
-      }
-      o += '"';
-      break;
-    }
-    case Json::Array: {
-      o += '[';
-      for (size_t i = 0; i < j.arr.size(); i++) {
-        if (i) o += ',';
-        dump_json(j.arr[i], o);
-      }
-      o += ']';
-      break;
-    }
-    case Json::Object: {
-      o += '{';
-      for (size_t i = 0; i < j.obj.size(); i++) {
-        if (i) o += ',';
-        Json key;
-        key.kind = Json::String;
-        key.str = j.obj[i].first;
-        dump_json(key, o);
-        o += ':';
-        dump_json(j.obj[i].second, o);
-      }
-      o += '}';
-      break;
+// The call: its arguments, fixed while it runs.
+struct FxRun {
+  Engine& E;
+  lk_result* res;
+  std::chrono::steady_clock::time_point t_start;
+  int glob_size;
+  bool dist;
+  int world, rank;
+};
+
+// One referenced expression while the call runs: its evaluation and its place in the join.
+struct Operand {
+  const FxExpr* x;
+  std::shared_ptr<lk_result> res;
+  std::vector<int> key_col;   // per key column: the operand's tag column
+  int64_t ts_lo = 0, ts_hi = 0;
+};
+
+// What the call reports; the stages fill it as they go.
+struct FxStats {
+  enum Kind { NO_OPERANDS, OFF_ROOT, ROOT } kind = NO_OPERANDS;
+  int world = 1, rank = 0;
+  double scan_ms = 0;                      // the operands' totals
+  unsigned long long rows_scanned = 0;
+  size_t n_dev = 0, n_up = 0;
+  std::string operands;                    // "operands": per variable, in evaluation order
+  size_t operand_rows = 0;                 // rank 0: the rows it joins ...
+  double operands_ms = 0;                  // ... and the time until they were placed
+  const char* mode = "dense";              // the device join's outcome
+  unsigned long long cells = 0;
+  int regrows = 0;
+  double scatter_ms = 0, eval_ms = 0, transfer_ms = 0;
+  size_t out_rows = 0;
+};
+
+// The operands' rows on rank 0: the bucket range they span.
+struct RowSpan {
+  int64_t base = INT64_MAX, last = INT64_MIN;
+  size_t total_rows = 0;
+};
+
+// The cell table after the scatter.
+struct Scattered {
+  FxTable T{};
+  bool dense = true;
+  unsigned long long ncells = 0;
+  double t0 = 0;   // ms since the call's start when the scatter began
+};
+
+// The combined rows' sources, fetched: (source operand, source gid) per output row.
+struct Joined {
+  std::vector<int32_t> src_op;
+  std::vector<uint32_t> src_gid;
+};
+
+std::string fixed6(double v) {
+  char b[64];
+  snprintf(b, sizeof(b), "%.6f", v);
+  return b;
+}
+
+// The stats text of all three outcomes: no operand (NO_OPERANDS), a rank that joins nothing (OFF_ROOT), rank 0 (ROOT).
+void write_stats(const FxRun& c, const FxStats& s) {
+  std::string o = std::string("{\"scan_ms\":") + (s.kind == FxStats::NO_OPERANDS ? "0" : fixed6(s.scan_ms)) +
+                  ",\"total_ms\":" + fixed6(ms_since(c.t_start)) + ",\"rows_scanned\":" + std::to_string(s.rows_scanned) +
+                  ",\"cells\":" + std::to_string(s.cells);
+  if (s.kind != FxStats::NO_OPERANDS) o += ",\"operand_rows\":" + std::to_string(s.operand_rows);
+  if (s.kind == FxStats::ROOT)
+    o += ",\"operands_ms\":" + fixed6(s.operands_ms) + ",\"scatter_ms\":" + fixed6(s.scatter_ms) + ",\"eval_ms\":" +
+         fixed6(s.eval_ms) + ",\"transfer_ms\":" + fixed6(s.transfer_ms) + ",\"link_bytes\":" + std::to_string(s.out_rows * 24);
+  o += std::string(",\"formula\":{\"mode\":\"") + s.mode + "\",\"cells\":" + std::to_string(s.cells) +
+       ",\"operands_on_device\":" + std::to_string(s.n_dev) + ",\"operands_uploaded\":" + std::to_string(s.n_up) +
+       ",\"regrows\":" + std::to_string(s.regrows) + ",\"world\":" + std::to_string(s.world) + ",\"rank\":" +
+       std::to_string(s.rank) + ",\"operands\":[" + s.operands + "]}}";
+  c.res->stats = o;
+}
+
+// ---- operands: merged rows (ts, value, group id) on the device ----
+void evaluate_operand(const FxRun& c, Operand& o) {
+  std::vector<const char*> pp;
+  for (auto& p : o.x->paths) pp.push_back(p.c_str());
+  const int32_t* shard = o.x->shard.empty() ? nullptr : o.x->shard.data();
+  if (!o.x->uploaded)
+    evaluate_keep_device(c.E, o.x->R, pp.data(), pp.size(), c.glob_size, shard, c.dist, o.res.get());
+  else if (c.dist)
+    evaluate_comm_held(c.E, o.x->push_down, pp.data(), pp.size(), c.glob_size, shard, o.res.get());
+  else
+    evaluate(c.E, o.x->push_down, pp.data(), pp.size(), c.glob_size, LK_MERGED, nullptr, false, o.res.get());
+}
+
+// A distributed operand with its closing agreement.  Its own collectives fail every rank together; what a rank meets
+// alone behind the last of them (rank 0 folding the gathered tables, placing the kept rows) is agreed on here, so no
+// rank starts the next operand's collectives while another unwinds.  Every rank passes the `merge` fault point.
+void evaluate_operand_agreed(const FxRun& c, Operand& o) {
+  int code = 0;
+  std::string msg;
+  try {
+    evaluate_operand(c, o);
+    fault_point(c.E, "merge");
+  } catch (const PlanError& e) {
+    code = e.code, msg = e.what();
+  } catch (const JsonError& e) {
+    code = LK_ERR_ARG, msg = e.what();
+  } catch (const std::bad_alloc&) {
+    code = LK_ERR_MEMORY, msg = "out of host memory";
+  } catch (const std::exception& e) {
+    code = LK_ERR_DEVICE, msg = e.what();
+  }
+  CtxLease X(c.E);
+  X->pend_code = 0;
+  X->pend_msg.clear();
+  comm_agree(c.E, *X, code, msg.empty() ? std::string() : "formula: expression " + o.x->var + ": " + msg);
+}
+
+// Every operand, in the gate's evaluation order; a distributed call holds comm_mu over all of them.
+void run_operands(const FxRun& c, const FxCall& call, std::vector<Operand>& ops, FxStats& st) {
+  std::unique_lock<std::mutex> comm_lock;
+  if (c.dist) comm_lock = std::unique_lock<std::mutex>(c.E.comm_mu);   // one hold over every operand's collectives
+  for (size_t k : call.order) {
+    Operand& o = ops[k];
+    o.res = std::make_shared<lk_result>();
+    if (c.dist) evaluate_operand_agreed(c, o);
+    else evaluate_operand(c, o);
+    (o.x->uploaded ? st.n_up : st.n_dev)++;
+    st.rows_scanned += o.res->rows_scanned;
+    st.scan_ms += o.res->scan_ms;
+    st.operands += std::string(st.operands.empty() ? "" : ",") + "{\"var\":\"" + json_escape(o.x->var) + "\",\"reduce\":\"" +
+                   json_escape(o.res->reduce) + "\",\"rows\":" + std::to_string(o.res->nrows) + ",\"kept\":" +
+                   (o.x->uploaded ? "false" : "true") + "}";
+  }
+}
+
+// Rank 0 looks at the rows for the first time: a host-assembled operand's rows are uploaded; the kept rows ascend in
+// time, so their first and last timestamp bound the buckets.
+void place_rows(const FxRun& c, std::vector<Operand>& ops) {
+  HIP_TRY(hipSetDevice(c.E.device));
+  for (Operand& o : ops) {
+    lk_result& r = *o.res;
+    if (r.exemplar) throw PlanError(LK_ERR_UNSUPPORTED, "formula: expression " + o.x->var + ": rows with per-row tags");
+    if (r.nrows > 0xffffffffull) throw PlanError(LK_ERR_UNSUPPORTED, "formula: expression " + o.x->var + " has 2^32 rows or more");
+    if (!r.nrows) continue;
+    const size_t n = r.nrows;
+    if (o.x->uploaded) {
+      HIP_TRY(hipMalloc(&r.dev_rows, n * 20 + 64));
+      uint8_t* d = static_cast<uint8_t*>(r.dev_rows);
+      HIP_TRY(hipMemcpy(d, r.ts, n * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(d + n * 8, r.val, n * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(d + n * 16, r.gid, n * 4, hipMemcpyHostToDevice));
+      o.ts_lo = r.ts[0];
+      o.ts_hi = r.ts[n - 1];
+    } else {
+      const int64_t* dts = static_cast<const int64_t*>(r.dev_rows);
+      HIP_TRY(hipMemcpy(&o.ts_lo, dts, 8, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&o.ts_hi, dts + (n - 1), 8, hipMemcpyDeviceToHost));
     }
   }
 }
 
-std::string lower_trim(std::string s) {
-  size_t a = 0, b = s.size();
-  while (a < b && isspace(static_cast<unsigned char>(s[a]))) a++;
-  while (b > a && isspace(static_cast<unsigned char>(s[b - 1]))) b--;
-  s = s.substr(a, b - a);
-  for (char& c : s) c = char(tolower(static_cast<unsigned char>(c)));
+// The result's tag columns: the union of the operands' tag columns, in order of first appearance; the span of the rows.
+RowSpan span_rows(const std::vector<Operand>& ops, lk_result* res) {
+  for (const Operand& o : ops)
+    for (auto& tn : o.res->tag_names)
+      if (std::find(res->tag_names.begin(), res->tag_names.end(), tn) == res->tag_names.end()) res->tag_names.push_back(tn);
+  RowSpan s;
+  for (const Operand& o : ops)
+    if (o.res->nrows) {
+      s.base = std::min(s.base, o.ts_lo);
+      s.last = std::max(s.last, o.ts_hi);
+      s.total_rows += o.res->nrows;
+    }
   return s;
 }
 
-// ASTUtils.getTransformerFunc (ASTUtils.scala:190-219) as one IEEE operation: identity, x secs or / secs, with
-// ChartType.fromStr (model/query/common/ChartType.scala:41-47; default "count", ASTUtils.scala:350) and
-// MetricType.fromStr (MetricType.scala:65-73; default gauge, ASTUtils.scala:298-303).
-int transformer_of(const Request& R, const Json& base_expr, const std::string& var) {
-  const std::string ct = lower_trim(R.has_chart ? R.chart_type : "count");
-  if (ct != "count" && ct != "rate") throw PlanError(LK_ERR_ARG, "formula: " + var + ": unknown chart type " + R.chart_type);
-  std::string mt = "gauge";
-  if (const Json* m = base_expr.get("metricType"); m && m->is_str()) mt = lower_trim(m->str);
-  if (mt == "count") mt = "counter";
-  if (mt != "rate" && mt != "counter" && mt != "gauge" && mt != "histogram")
-    throw PlanError(LK_ERR_ARG, "formula: " + var + ": unknown metric type " + mt);
-  if (R.dataset == "metrics") {
-    if (ct == "count" && mt == "rate") return FX_XF_MUL;
-    if (ct == "rate" && mt == "counter") return FX_XF_DIV;
-    return FX_XF_NONE;
-  }
-  return ct == "rate" ? FX_XF_DIV : FX_XF_NONE;
-}
-
+// ---- union group space: the operands' tag columns as formula_join.hpp reads them ----
 // dim id -> tag text of a name / groupBy tag column (lk_result::own_tag_gid for one dim id); nullptr: the tag is absent
 const char* dim_text(const lk_result::TagCol& t, uint32_t d) {
   if (t.hidden) return nullptr;
@@ -137,551 +232,234 @@ const char* dim_text(const lk_result::TagCol& t, uint32_t d) {
   return (s.empty() || s == "null") ? nullptr : s.c_str();
 }
 
-struct Operand {
-  std::string var;
-  std::shared_ptr<const Request> R;
-  std::vector<std::string> paths;
-  std::vector<int32_t> shard;   // distributed: the rank of every path ("shard"); empty: i % world
-  std::shared_ptr<lk_result> res;
-  bool uploaded = false;
-  int xform = FX_XF_NONE;
-  std::vector<int> key_col;   // per key column: the operand's tag column
-  int64_t ts_lo = 0, ts_hi = 0;
-};
-
-using TagList = std::vector<std::pair<std::string, std::string>>;
-
-}  // namespace
-
-// Distributed (lk_eval_formula_dist; DESIGN.md §7.6 "Distributed"): a rank is a pod.  Every operand is one sharded merged
-// evaluation whose rows land on rank 0 (kept on its device, or uploaded by it), the join runs on rank 0 alone.  comm_mu is
-// held for the whole call; the operands run in ascending byte order of their variable names, each closed by one
-// agreement of the ranks' outcomes, so every rank issues the same collectives and all fail at the same operand.
-// Everything decided before the first collective -- the parser, the gate, the shard check -- reads the request alone.
-int evaluate_formula(Engine& E, const std::string& json, int glob_size, bool dist, lk_result* res) {
-  const auto t_start = std::chrono::steady_clock::now();
-  if (glob_size <= 0) glob_size = 10;
-  Json top = Json::parse(json);
-  const Json* ftext = top.get("formula");
-  const Json* exprs = top.get("expressions");
-  if (!ftext || !ftext->is_str()) throw PlanError(LK_ERR_ARG, "formula: missing \"formula\"");
-  if (!exprs || !exprs->is_obj()) throw PlanError(LK_ERR_ARG, "formula: missing \"expressions\"");
-  std::vector<std::string> names;
-  for (auto& kv : exprs->obj) names.push_back(kv.first);
-
-  // ---- parse; leaves renumbered over the referenced expressions, in the order of `expressions` ----
-  FxProgram prog;
-  {
-    std::string err;
-    const int rc = parse_formula(ftext->str, names, prog, err);
-    if (rc) throw PlanError(rc, err);
-  }
-  std::vector<int> leaf_of(names.size(), -1);
-  std::vector<Operand> ops;
-  for (size_t v = 0; v < names.size(); v++) {
-    bool used = false;
-    for (int i = 0; i < prog.n; i++) used = used || (prog.ops[i].op == FX_LEAF && prog.ops[i].leaf == int32_t(v));
-    if (!used) continue;
-    leaf_of[v] = int(ops.size());
-    ops.emplace_back();
-    ops.back().var = names[v];
-  }
-  for (int i = 0; i < prog.n; i++)
-    if (prog.ops[i].op == FX_LEAF) prog.ops[i].leaf = leaf_of[size_t(prog.ops[i].leaf)];
-  if (ops.size() > size_t(FX_MAXLEAF))
-    throw PlanError(LK_ERR_UNSUPPORTED, "formula: more than " + std::to_string(FX_MAXLEAF) + " expressions referenced");
-
-  const int world = dist ? comm_world(E) : 1, rank = dist ? comm_rank(E) : 0;
-  char fstats[512];
-  auto finish_empty = [&]() {
-    res->exemplar = true;
-    snprintf(fstats, sizeof(fstats),
-             "{\"scan_ms\":0,\"total_ms\":%.6f,\"rows_scanned\":0,\"cells\":0,\"formula\":{\"mode\":\"dense\",\"cells\":0,"
-             "\"operands_on_device\":0,\"operands_uploaded\":0,\"regrows\":0,\"world\":%d,\"rank\":%d,\"operands\":[]}}",
-             ms_since(t_start), world, rank);
-    res->stats = fstats;
-    return int(LK_OK);
-  };
-  if (ops.empty()) return finish_empty();   // no variable: no SketchGroup reaches the formula, no rows
-
-  // ---- gate (every rule depends on the requests alone) ----
-  auto refuse = [](const std::string& why) { throw PlanError(LK_ERR_UNSUPPORTED, "formula: " + why); };
-  std::vector<std::string> key_cols;   // the groupBy set, sorted (toGroupByKey sorts, ASTUtils.scala:87-89)
-  int64_t step = 0;
-  for (size_t k = 0; k < ops.size(); k++) {
-    Operand& o = ops[k];
-    const Json& ex = *exprs->get(o.var);
-    const Json* pd = ex.get("pushDown");
-    if (!pd || !pd->is_obj()) throw PlanError(LK_ERR_ARG, "formula: expression " + o.var + " has no pushDown");
-    std::string text;
-    dump_json(*pd, text);
-    o.R = E.parse_cached(text);
-    if (const Json* ps = ex.get("paths"); ps && ps->is_arr())
-      for (auto& p : ps->arr) o.paths.push_back(p.scalar_text());
-    if (o.paths.size() != o.R->segments.size())
-      throw PlanError(LK_ERR_ARG, "formula: expression " + o.var + ": paths must match segmentRequests");
-    if (const Json* sh = ex.get("shard"); dist && sh && sh->kind != Json::Null) {
-      if (!sh->is_arr() || sh->arr.size() != o.paths.size())
-        throw PlanError(LK_ERR_ARG, "formula: expression " + o.var + ": shard must have one rank per path");
-      for (auto& v : sh->arr) {
-        const int64_t r = v.as_i64();
-        if (r < 0 || r >= world)
-          throw PlanError(LK_ERR_ARG, "formula: expression " + o.var + ": shard rank " + std::to_string(r) + " outside the world");
-        o.shard.push_back(int32_t(r));
-      }
-    }
-    const Request& R = *o.R;
-    if (R.is_tag_query) refuse("expression " + o.var + " is a tag query");
-    if (!R.has_chart) refuse("expression " + o.var + " has no chart (an exemplar query has no value to combine)");
-    if (R.has_extract || R.has_compute) refuse("expression " + o.var + " uses extract / compute");
-    const bool pct = R.aggregation.size() > 1 && R.aggregation[0] == 'p';
-    if (pct && R.dataset == "metrics" && !R.field_chart())
-      refuse("expression " + o.var + ": metrics percentiles are assembled per row on the host");
-    std::vector<std::string> gb = R.group_bys;
-    std::sort(gb.begin(), gb.end());
-    gb.erase(std::unique(gb.begin(), gb.end()), gb.end());
-    if (k == 0) key_cols = gb;
-    else if (gb != key_cols)
-      refuse("expressions " + ops[0].var + " and " + o.var + " have different groupBy sets");
-    for (auto& s : R.segments) {
-      if (s.step <= 0) throw PlanError(LK_ERR_ARG, "formula: expression " + o.var + ": stepInMillis must be positive");
-      if (step && s.step != step) throw PlanError(LK_ERR_ARG, "formula: the expressions' steps differ");
-      step = s.step;
-    }
-    o.xform = transformer_of(R, *pd->get("baseExpr"), o.var);
-    // values assembled on the host (DDSketch quantiles, HLL estimates): evaluated as usual, then uploaded
-    o.uploaded = pct || R.aggregation == "ces" || (R.rollup.find("ces") != std::string::npos && R.dataset != "metrics");
-  }
-  if (key_cols.size() > size_t(FX_MAXCOL))
-    refuse("more than " + std::to_string(FX_MAXCOL) + " groupBy columns");
-  const double secs = double(step / 1000);   // the Long quotient stepInMillis / 1000 (ASTUtils.scala:192)
-
-  if (dist && !E.comm) throw PlanError(LK_ERR_ARG, "lk_comm_init has not been called");
-
-  // ---- operands: merged rows (ts, value, group id) on the device ----
-  unsigned long long rows_scanned = 0;
-  double scan_ms = 0;
-  size_t n_dev = 0, n_up = 0;
-  // evaluated in ascending byte order of the variable names: the order of a distributed call's collectives must not
-  // depend on how a rank's caller ordered the JSON object (leaf numbers and a constant's tags keep reading `expressions`)
-  std::vector<size_t> order(ops.size());
-  for (size_t k = 0; k < ops.size(); k++) order[k] = k;
-  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return ops[a].var < ops[b].var; });
-  std::unique_lock<std::mutex> comm_lock;
-  if (dist) comm_lock = std::unique_lock<std::mutex>(E.comm_mu);   // one hold over every operand's collectives
-  std::string op_stats;   // "operands": per variable, in evaluation order
-  for (size_t k : order) {
-    Operand& o = ops[k];
-    o.res = std::make_shared<lk_result>();
-    std::vector<const char*> pp;
-    for (auto& p : o.paths) pp.push_back(p.c_str());
-    const int32_t* shard = o.shard.empty() ? nullptr : o.shard.data();
-    auto run = [&] {
-      if (o.uploaded) {
-        std::string text;
-        dump_json(*exprs->get(o.var)->get("pushDown"), text);
-        if (dist) evaluate_comm_held(E, text, pp.data(), pp.size(), glob_size, shard, o.res.get());
-        else evaluate(E, text, pp.data(), pp.size(), glob_size, LK_MERGED, nullptr, false, o.res.get());
-      } else {
-        evaluate_keep_device(E, o.R, pp.data(), pp.size(), glob_size, shard, dist, o.res.get());
-      }
-    };
-    if (!dist) {
-      run();
-    } else {
-      // The operand's closing agreement.  Its own collectives fail every rank together; what a rank meets alone behind
-      // the last of them (rank 0 folding the gathered tables, placing the kept rows) is agreed on here, so no rank
-      // starts the next operand's collectives while another unwinds.  Every rank passes the `merge` fault point.
-      int code = 0;
-      std::string msg;
-      try {
-        run();
-        fault_point(E, "merge");
-      } catch (const PlanError& e) {
-        code = e.code, msg = e.what();
-      } catch (const JsonError& e) {
-        code = LK_ERR_ARG, msg = e.what();
-      } catch (const std::bad_alloc&) {
-        code = LK_ERR_MEMORY, msg = "out of host memory";
-      } catch (const std::exception& e) {
-        code = LK_ERR_DEVICE, msg = e.what();
-      }
-      CtxLease X(E);
-      X->pend_code = 0;
-      X->pend_msg.clear();
-      comm_agree(E, *X, code, msg.empty() ? std::string() : "formula: expression " + o.var + ": " + msg);
-    }
-    (o.uploaded ? n_up : n_dev)++;
-    std::string reduce = "none";
-    if (!o.res->stats.empty()) {
-      try {
-        Json st = Json::parse(o.res->stats);
-        if (const Json* x = st.get("rows_scanned")) rows_scanned += (unsigned long long)x->as_i64();
-        if (const Json* x = st.get("scan_ms")) scan_ms += x->num;
-        if (const Json* x = st.get("reduce"); x && x->is_str()) reduce = x->str;
-      } catch (const JsonError&) {
-      }
-    }
-    op_stats += std::string(op_stats.empty() ? "" : ",") + "{\"var\":\"" + json_escape(o.var) + "\",\"reduce\":\"" + json_escape(reduce) +
-                "\",\"rows\":" + std::to_string(o.res->nrows) + ",\"kept\":" + (o.uploaded ? "false" : "true") + "}";
-  }
-  const std::string fx_tail = ",\"world\":" + std::to_string(world) + ",\"rank\":" + std::to_string(rank) + ",\"operands\":[" + op_stats + "]}}";
-  // Behind the last operand's last collective: from here a failure unwinds this rank alone.  The other ranks return
-  // their empty result; rank 0 looks at the rows for the first time.
-  if (rank != 0) {
-    res->exemplar = true;
-    char b0[384];
-    snprintf(b0, sizeof(b0),
-             "{\"scan_ms\":%.6f,\"total_ms\":%.6f,\"rows_scanned\":%llu,\"cells\":0,\"operand_rows\":0,\"formula\":{\"mode\":\"dense\","
-             "\"cells\":0,\"operands_on_device\":%zu,\"operands_uploaded\":%zu,\"regrows\":0",
-             scan_ms, ms_since(t_start), rows_scanned, n_dev, n_up);
-    res->stats = b0 + fx_tail;
-    return LK_OK;
-  }
-  HIP_TRY(hipSetDevice(E.device));
-  for (Operand& o : ops) {
-    lk_result& r = *o.res;
-    if (r.exemplar) refuse("expression " + o.var + ": rows with per-row tags");
-    if (r.nrows > 0xffffffffull) refuse("expression " + o.var + " has 2^32 rows or more");
-    if (!r.nrows) continue;
-    const size_t n = r.nrows;
-    if (o.uploaded) {
-      HIP_TRY(hipMalloc(&r.dev_rows, n * 20 + 64));
-      uint8_t* d = static_cast<uint8_t*>(r.dev_rows);
-      HIP_TRY(hipMemcpy(d, r.ts, n * 8, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(d + n * 8, r.val, n * 8, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(d + n * 16, r.gid, n * 4, hipMemcpyHostToDevice));
-      o.ts_lo = r.ts[0];
-      o.ts_hi = r.ts[n - 1];
-    } else {   // rows ascend in time: the first and the last timestamp bound the buckets
-      const int64_t* dts = static_cast<const int64_t*>(r.dev_rows);
-      HIP_TRY(hipMemcpy(&o.ts_lo, dts, 8, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(&o.ts_hi, dts + (n - 1), 8, hipMemcpyDeviceToHost));
-    }
-  }
-  const double operands_ms = ms_since(t_start);
-
-  // ---- result tag columns: the union of the operands' tag columns, in order of first appearance ----
-  for (Operand& o : ops)
-    for (auto& tn : o.res->tag_names)
-      if (std::find(res->tag_names.begin(), res->tag_names.end(), tn) == res->tag_names.end()) res->tag_names.push_back(tn);
-  res->exemplar = true;   // tags materialized per row (ex_tags): no bulk export of group ids
-
-  int64_t base = INT64_MAX, last = INT64_MIN;
-  size_t total_rows = 0;
-  for (Operand& o : ops)
-    if (o.res->nrows) {
-      base = std::min(base, o.ts_lo);
-      last = std::max(last, o.ts_hi);
-      total_rows += o.res->nrows;
-    }
-  char buf[768];
-  auto write_stats = [&](const char* mode, unsigned long long cells, int regrows, double scatter_ms, double eval_ms,
-                         double transfer_ms, size_t out_rows) {
-    snprintf(buf, sizeof(buf),
-             "{\"scan_ms\":%.6f,\"total_ms\":%.6f,\"rows_scanned\":%llu,\"cells\":%llu,\"operand_rows\":%zu,"
-             "\"operands_ms\":%.6f,\"scatter_ms\":%.6f,\"eval_ms\":%.6f,\"transfer_ms\":%.6f,\"link_bytes\":%zu,"
-             "\"formula\":{\"mode\":\"%s\",\"cells\":%llu,\"operands_on_device\":%zu,\"operands_uploaded\":%zu,"
-             "\"regrows\":%d",
-             scan_ms, ms_since(t_start), rows_scanned, cells, total_rows, operands_ms, scatter_ms, eval_ms, transfer_ms,
-             out_rows * 24, mode, cells, n_dev, n_up, regrows);
-    res->stats = buf + fx_tail;
-  };
-  if (!total_rows) {
-    write_stats("dense", 0, 0, 0, 0, 0, 0);
-    return LK_OK;
-  }
-
-  // ---- union group space: per key column the union of the operands' dimension values; id 0 = absent ("") ----
-  const size_t nk = key_cols.size();
-  std::vector<std::unordered_map<std::string, uint32_t>> uni(nk);
-  // A column every operand reads through the same engine dictionary (unrestricted groupBy, one generation) needs no
-  // table: union id = dim id + 1, the absent ids (NULL, "", "null") read 0 -- a 10M-value column costs nothing here.
-  // Values met outside the dictionary's dims (queryTags) take ids past them.
-  std::vector<char> ident(nk, 0);
-  std::vector<GlobalDict*> ident_gd(nk, nullptr);
-  std::vector<uint32_t> ident_max(nk, 0), ident_nl0(nk, IdMap::kNone), ident_nl1(nk, IdMap::kNone);
+void find_key_columns(const std::vector<std::string>& key_cols, std::vector<Operand>& ops) {
   for (Operand& o : ops) {
     if (!o.res->nrows) continue;
-    o.key_col.assign(nk, -1);
-    for (size_t j = 0; j < nk; j++) {
-      const auto& gbs = o.R->group_bys;
+    o.key_col.assign(key_cols.size(), -1);
+    for (size_t j = 0; j < key_cols.size(); j++) {
+      const auto& gbs = o.x->R->group_bys;
       const size_t at = size_t(std::find(gbs.begin(), gbs.end(), key_cols[j]) - gbs.begin());
       if (1 + at >= o.res->tcols.size()) throw PlanError(LK_ERR_DEVICE, "internal: groupBy column missing from the operand");
       o.key_col[j] = int(1 + at);
     }
   }
-  for (size_t j = 0; j < nk; j++) {
-    const StableStrs* dict = nullptr;
-    bool ok = true, any = false;
-    for (Operand& o : ops) {
-      if (!o.res->nrows) continue;
-      const lk_result::TagCol& t = o.res->tcols[size_t(o.key_col[j])];
-      const bool plain = !t.hidden && !t.shared && t.local.empty() && !t.order && t.dict && !t.null_value &&
-                         t.ndim <= 0xfffffff0ull && t.dim_null + 1 == t.ndim;
-      ok = ok && plain && (!any || t.dict == dict);
-      dict = t.dict;
-      any = true;
-      ident_max[j] = std::max<uint32_t>(ident_max[j], uint32_t(t.ndim));
-    }
-    if (!ok || !any) continue;
-    GlobalDict& gd = E.dict(key_cols[j]);
-    std::lock_guard<std::mutex> g(gd.mu);
-    if (gd.vals.get() != dict) continue;   // (another generation: take the tables)
-    ident[j] = 1;
-    ident_gd[j] = &gd;
-    ident_nl0[j] = gd.ids.find("");
-    ident_nl1[j] = gd.ids.find("null");
-  }
-  auto union_id = [&](size_t j, const char* s) -> uint32_t {
-    if (!s || !*s) return 0;
-    if (ident[j]) {
-      uint32_t id;
-      {
-        std::lock_guard<std::mutex> g(ident_gd[j]->mu);
-        id = ident_gd[j]->ids.find(s);
-      }
-      if (id != IdMap::kNone && id + 1 < ident_max[j]) return id + 1;   // a dim id of the dictionary (not dim_null)
-      auto it = uni[j].find(s);
-      if (it != uni[j].end()) return it->second;
-      const uint32_t nid = ident_max[j] + 1 + uint32_t(uni[j].size());
-      uni[j].emplace(s, nid);
-      return nid;
-    }
-    auto it = uni[j].find(s);
-    if (it != uni[j].end()) return it->second;
-    const uint32_t id = uint32_t(uni[j].size()) + 1;
-    uni[j].emplace(s, id);
-    return id;
-  };
-  std::vector<std::vector<std::vector<uint32_t>>> maps(ops.size(), std::vector<std::vector<uint32_t>>(nk));
-  std::vector<std::vector<uint32_t>> name_rank(ops.size());
-  std::vector<std::vector<uint32_t>> qt_ids(ops.size(), std::vector<uint32_t>(nk, 0));
-  std::vector<uint32_t> qt_rank(ops.size(), 1);
-  for (size_t k = 0; k < ops.size(); k++) {
-    Operand& o = ops[k];
-    const lk_result& r = *o.res;
-    if (!r.nrows) continue;   // (an expression without rows -- no segments, an empty glob -- is absent everywhere)
-    if (r.tcols.empty()) throw PlanError(LK_ERR_DEVICE, "internal: operand without tag columns");
-    for (size_t j = 0; j < nk; j++) {
-      if (ident[j]) continue;
-      const lk_result::TagCol& tc = r.tcols[size_t(o.key_col[j])];
-      if (tc.ndim > 0xffffffffull) refuse("group dimension too large");
-      auto& m = maps[k][j];
-      m.resize(size_t(tc.ndim));
-      for (uint32_t d = 0; d < uint32_t(tc.ndim); d++) m[d] = union_id(j, dim_text(tc, d));
-    }
-    // the name dimension is not part of the key: its rank, by text, decides the collapse (2 * order + 4)
-    const lk_result::TagCol& nc = r.tcols[0];
-    std::vector<std::string> texts;
-    std::vector<const char*> nt(size_t(nc.ndim), nullptr);
-    for (uint32_t d = 0; d < uint32_t(nc.ndim); d++) {
-      nt[d] = dim_text(nc, d);
-      if (nt[d]) texts.emplace_back(nt[d]);
-    }
-    std::sort(texts.begin(), texts.end());
-    texts.erase(std::unique(texts.begin(), texts.end()), texts.end());
-    name_rank[k].assign(size_t(nc.ndim), FX_RANK_ABSENT);
-    for (uint32_t d = 0; d < uint32_t(nc.ndim); d++)
-      if (nt[d])
-        name_rank[k][d] = 2u * uint32_t(std::lower_bound(texts.begin(), texts.end(), std::string(nt[d])) - texts.begin()) + 4u;
-    // a row whose own tags are all absent takes its glob's queryTags (Commons.scala:450-452; merged rows: the first
-    // glob's): its key reads the groupBy columns there, and its rank is its sorted tag list's place among the lists
-    // of the named rows of that key (2 * place + 3), or past the key's row without a name tag (formula_kernels.hpp)
-    TagList qt;
-    if (!r.qt_of_glob.empty())
-      for (auto& kv : r.qt_of_glob[0]) qt.emplace_back(r.tag_names[kv.first], kv.second ? kv.second : "");
-    std::sort(qt.begin(), qt.end());
-    TagList rest;   // the groupBy tags a named row of that key carries
-    for (size_t j = 0; j < nk; j++) {
-      std::string v;
-      for (auto& kv : qt)
-        if (kv.first == key_cols[j]) v = kv.second;
-      qt_ids[k][j] = union_id(j, v.c_str());
-      if (!v.empty()) rest.emplace_back(r.tag_names[size_t(o.key_col[j])], v);
-    }
-    std::sort(rest.begin(), rest.end());
-    bool noname_last = false;   // as fx_scatter ranks the key's row without a name tag
-    for (auto& kv : rest) noname_last = noname_last || kv.first > r.tag_names[0];
-    uint32_t place = 0;   // (no queryTags: the empty list sorts first)
-    for (auto& nm : texts) {
-      if (qt.empty()) break;
-      TagList l = rest;
-      l.emplace_back(r.tag_names[0], nm);
-      std::sort(l.begin(), l.end());
-      if (l < qt) place++;
-    }
-    qt_rank[k] = 2u * place + 3u;
-    if (!rest.empty()) {
-      if (!noname_last && place == 0 && qt < rest) qt_rank[k] = 0u;
-      if (noname_last && place == texts.size() && rest < qt) qt_rank[k] = FX_RANK_NONAME_LAST + 1u;
-    }
-  }
-  std::vector<unsigned long long> ustride(nk, 1);
-  unsigned long long U = 1;
-  for (size_t j = nk; j-- > 0;) {
-    ustride[j] = U;
-    const unsigned long long n = (unsigned long long)uni[j].size() + 1 + (ident[j] ? ident_max[j] : 0);
-    if (U > (~0ull) / n) refuse("the union group space does not fit in 64 bits");
-    U *= n;
-  }
-  const unsigned long long nbuckets = (unsigned long long)((last - base) / step) + 1;
-  if (nbuckets > (1ull << 26)) refuse("more than 2^26 buckets");
-  if (U > (~0ull - 1) / nbuckets) refuse("the cell key (buckets x union groups) does not fit in 64 bits");
-  const unsigned long long nkeys = nbuckets * U;
+}
 
-  // ---- device: tables, scatter, evaluate, write ----
-  CtxLease X(E);
-  hipStream_t st = X->stream;
-  const int L = int(ops.size());
-  // one staging block: per operand the key column maps and the name rank
-  size_t tab_words = 0;
-  for (size_t k = 0; k < ops.size(); k++) {
-    for (auto& m : maps[k]) tab_words += m.size();
-    tab_words += name_rank[k].size();
+// A column every operand reads through the same engine dictionary (unrestricted groupBy, one generation) needs no
+// table: union id = dim id + 1, the absent ids (NULL, "", "null") read 0 -- a 10M-value column costs nothing here.
+// Values met outside the dictionary's dims (queryTags) take ids past them.
+FxIdentity identity_column(Engine& E, const std::string& col, size_t j, const std::vector<Operand>& ops) {
+  FxIdentity id;
+  const StableStrs* dict = nullptr;
+  bool ok = true, any = false;
+  for (const Operand& o : ops) {
+    if (!o.res->nrows) continue;
+    const lk_result::TagCol& t = o.res->tcols[size_t(o.key_col[j])];
+    const bool plain = !t.hidden && !t.shared && t.local.empty() && !t.order && t.dict && !t.null_value &&
+                       t.ndim <= 0xfffffff0ull && t.dim_null + 1 == t.ndim;
+    ok = ok && plain && (!any || t.dict == dict);
+    dict = t.dict;
+    any = true;
+    id.ndim = std::max<uint32_t>(id.ndim, uint32_t(t.ndim));
   }
-  uint32_t* d_tabs = static_cast<uint32_t*>(X->workspace("fx_tabs", tab_words * 4 + 64));
-  {
-    std::vector<uint32_t> h;
-    h.reserve(tab_words);
-    for (size_t k = 0; k < ops.size(); k++) {
-      for (auto& m : maps[k]) h.insert(h.end(), m.begin(), m.end());
-      h.insert(h.end(), name_rank[k].begin(), name_rank[k].end());
-    }
-    if (!h.empty()) HIP_TRY(hipMemcpyAsync(d_tabs, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));   // (h is pageable and leaves scope)
+  if (!ok || !any) return id;
+  GlobalDict* gd = &E.dict(col);
+  std::lock_guard<std::mutex> g(gd->mu);
+  if (gd->vals.get() != dict) return id;   // (another generation: take the tables)
+  id.on = true;
+  id.nl0 = gd->ids.find("");
+  id.nl1 = gd->ids.find("null");
+  id.dict_id = [gd](const char* s) {
+    std::lock_guard<std::mutex> g2(gd->mu);
+    return gd->ids.find(s);
+  };
+  return id;
+}
+
+FxOperandDims describe(const Operand& o) {
+  FxOperandDims d;
+  const lk_result& r = *o.res;
+  if (!r.nrows) return d;
+  if (r.tcols.empty()) throw PlanError(LK_ERR_DEVICE, "internal: operand without tag columns");
+  d.has_rows = true;
+  auto dim_of = [&r](size_t c) {
+    const lk_result::TagCol* t = &r.tcols[c];
+    return FxDim{r.tag_names[c], t->ndim, [t](uint32_t i) { return dim_text(*t, i); }};
+  };
+  d.name = dim_of(0);
+  for (int c : o.key_col) d.key.push_back(dim_of(size_t(c)));
+  if (!r.qt_of_glob.empty())
+    for (auto& kv : r.qt_of_glob[0]) d.query_tags.emplace_back(r.tag_names[kv.first], kv.second ? kv.second : "");
+  return d;
+}
+
+FxUnion union_space(Engine& E, const FxCall& call, std::vector<Operand>& ops, std::vector<FxIdentity>& ident) {
+  find_key_columns(call.key_cols, ops);
+  for (size_t j = 0; j < call.key_cols.size(); j++) ident.push_back(identity_column(E, call.key_cols[j], j, ops));
+  std::vector<FxOperandDims> dims;
+  for (const Operand& o : ops) dims.push_back(describe(o));
+  return fx_union_space(call.key_cols, dims, ident);
+}
+
+// ---- device: tables, scatter, evaluate, write ----
+// One staging block: per operand the key column maps and the name rank; the FxOperands that point into it.
+std::vector<FxOperand> stage_operands(CallCtx& X, const std::vector<Operand>& ops, const FxUnion& un,
+                                      const std::vector<FxIdentity>& ident) {
+  std::vector<uint32_t> h;
+  for (const FxOperandJoin& j : un.ops) {
+    for (auto& m : j.map) h.insert(h.end(), m.begin(), m.end());
+    h.insert(h.end(), j.name_rank.begin(), j.name_rank.end());
   }
+  uint32_t* d_tabs = static_cast<uint32_t*>(X.workspace("fx_tabs", h.size() * 4 + 64));
+  if (!h.empty()) HIP_TRY(hipMemcpyAsync(d_tabs, h.data(), h.size() * 4, hipMemcpyHostToDevice, X.stream));
+  HIP_TRY(hipStreamSynchronize(X.stream));   // (h is pageable and leaves scope)
   std::vector<FxOperand> fo(ops.size());
-  {
-    size_t off = 0;
-    for (size_t k = 0; k < ops.size(); k++) {
-      const lk_result& r = *ops[k].res;
-      FxOperand& f = fo[k];
-      memset(&f, 0, sizeof(f));
-      f.leaf = int(k);
-      if (!r.nrows) continue;
-      const size_t n = r.nrows;
-      const uint8_t* d = static_cast<const uint8_t*>(r.dev_rows);
-      f.ts = reinterpret_cast<const int64_t*>(d);
-      f.val = reinterpret_cast<const double*>(d + n * 8);
-      f.gid = reinterpret_cast<const uint32_t*>(d + n * 16);
-      f.nrows = uint32_t(n);
-      f.leaf = int(k);
-      f.ncols = int(nk);
-      for (size_t j = 0; j < nk; j++) {
-        const lk_result::TagCol& tc = r.tcols[size_t(ops[k].key_col[j])];
-        f.stride[j] = tc.stride ? tc.stride : 1;
-        f.ndim[j] = tc.ndim ? tc.ndim : 1;
-        f.ustride[j] = ustride[j];
-        f.map[j] = ident[j] ? nullptr : d_tabs + off;
-        off += maps[k][j].size();
-        f.dim_null[j] = tc.dim_null;
-        f.nl0[j] = ident_nl0[j];
-        f.nl1[j] = ident_nl1[j];
-        if (r.tag_names[size_t(ops[k].key_col[j])] > r.tag_names[0]) f.after_name |= 1u << j;
-        f.qt_u += (unsigned long long)qt_ids[k][j] * ustride[j];
-      }
-      f.name_stride = r.tcols[0].stride ? r.tcols[0].stride : 1;
-      f.name_ndim = r.tcols[0].ndim ? r.tcols[0].ndim : 1;
-      f.name_rank = d_tabs + off;
-      off += name_rank[k].size();
-      f.qt_rank = qt_rank[k];
+  size_t off = 0;
+  for (size_t k = 0; k < ops.size(); k++) {
+    const lk_result& r = *ops[k].res;
+    const FxOperandJoin& j = un.ops[k];
+    FxOperand& f = fo[k];
+    memset(&f, 0, sizeof(f));
+    f.leaf = int(k);
+    if (!r.nrows) continue;
+    const size_t n = r.nrows;
+    const uint8_t* d = static_cast<const uint8_t*>(r.dev_rows);
+    f.ts = reinterpret_cast<const int64_t*>(d);
+    f.val = reinterpret_cast<const double*>(d + n * 8);
+    f.gid = reinterpret_cast<const uint32_t*>(d + n * 16);
+    f.nrows = uint32_t(n);
+    f.ncols = int(ident.size());
+    for (size_t c = 0; c < ident.size(); c++) {
+      const lk_result::TagCol& tc = r.tcols[size_t(ops[k].key_col[c])];
+      f.stride[c] = tc.stride ? tc.stride : 1;
+      f.ndim[c] = tc.ndim ? tc.ndim : 1;
+      f.ustride[c] = un.ustride[c];
+      f.map[c] = ident[c].on ? nullptr : d_tabs + off;
+      off += j.map[c].size();
+      f.dim_null[c] = tc.dim_null;
+      f.nl0[c] = ident[c].nl0;
+      f.nl1[c] = ident[c].nl1;
     }
+    f.after_name = j.after_name;
+    f.qt_u = j.qt_u;
+    f.name_stride = r.tcols[0].stride ? r.tcols[0].stride : 1;
+    f.name_ndim = r.tcols[0].ndim ? r.tcols[0].ndim : 1;
+    f.name_rank = d_tabs + off;
+    off += j.name_rank.size();
+    f.qt_rank = j.qt_rank;
   }
-  const bool dense = nkeys <= E.formula_dense_max_cells;
-  unsigned long long ncells = nkeys;
-  if (!dense) {
-    unsigned long long want = E.formula_hash_slots ? E.formula_hash_slots : 2ull * total_rows;
-    ncells = 64;
-    while (ncells < want) ncells <<= 1;
+  return fo;
+}
+
+// Fills the cell table from every operand's rows; a full hash table regrows fourfold and scatters again.
+Scattered scatter(const FxRun& c, CallCtx& X, const FxCall& call, const std::vector<FxOperand>& fo, const RowSpan& span,
+                  const FxCells& cells, unsigned long long U, FxStats& st) {
+  hipStream_t stream = X.stream;
+  const unsigned long long L = fo.size();
+  Scattered s;
+  s.dense = cells.nkeys <= c.E.formula_dense_max_cells;
+  s.ncells = cells.nkeys;
+  if (!s.dense) {
+    const unsigned long long want = c.E.formula_hash_slots ? c.E.formula_hash_slots : 2ull * span.total_rows;
+    s.ncells = 64;
+    while (s.ncells < want) s.ncells <<= 1;
   }
-  int regrows = 0;
-  FxTable T{};
-  uint32_t* d_flags = static_cast<uint32_t*>(X->workspace("fx_flags", 64));
-  const double t_scatter0 = ms_since(t_start);
+  uint32_t* d_flags = static_cast<uint32_t*>(X.workspace("fx_flags", 64));
+  s.t0 = ms_since(c.t_start);
   for (;;) {
-    if (ncells > (1ull << 34) / (unsigned long long)L) throw PlanError(LK_ERR_MEMORY, "formula: cell table too large");
-    uint8_t* tb = static_cast<uint8_t*>(X->workspace("fx_table", size_t(ncells) * 8 * size_t(L + (dense ? 0 : 1)) + 256));
-    T.slots = reinterpret_cast<unsigned long long*>(tb);
-    T.keys = dense ? nullptr : T.slots + ncells * (unsigned long long)L;
-    T.ncells = ncells;
-    T.U = U;
-    T.nbuckets = nbuckets;
-    T.base = base;
-    T.step = step;
-    T.flags = d_flags;
-    T.live = d_flags + 1;
-    T.nleaves = L;
-    HIP_TRY(hipMemsetAsync(d_flags, 0, 64, st));
-    HIP_TRY(launch_fx_fill(T.slots, ncells * (unsigned long long)(L + (dense ? 0 : 1)), st));
-    for (auto& f : fo) HIP_TRY(launch_fx_scatter(T, f, st));
+    if (s.ncells > (1ull << 34) / L) throw PlanError(LK_ERR_MEMORY, "formula: cell table too large");
+    const unsigned long long words = s.ncells * (L + (s.dense ? 0 : 1));
+    s.T.slots = static_cast<unsigned long long*>(X.workspace("fx_table", size_t(words) * 8 + 256));
+    s.T.keys = s.dense ? nullptr : s.T.slots + s.ncells * L;
+    s.T.ncells = s.ncells;
+    s.T.U = U;
+    s.T.nbuckets = cells.nbuckets;
+    s.T.base = span.base;
+    s.T.step = call.step;
+    s.T.flags = d_flags;
+    s.T.live = d_flags + 1;
+    s.T.nleaves = int(L);
+    HIP_TRY(hipMemsetAsync(d_flags, 0, 64, stream));
+    HIP_TRY(launch_fx_fill(s.T.slots, words, stream));
+    for (auto& f : fo) HIP_TRY(launch_fx_scatter(s.T, f, stream));
     uint32_t fl = 0;
-    HIP_TRY(hipMemcpyAsync(&fl, d_flags, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (fl & FX_FLAG_OFFGRID) refuse("an expression's timestamps are off the step grid");
+    HIP_TRY(hipMemcpyAsync(&fl, d_flags, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (fl & FX_FLAG_OFFGRID) throw PlanError(LK_ERR_UNSUPPORTED, "formula: an expression's timestamps are off the step grid");
     if (fl & FX_FLAG_RANGE) throw PlanError(LK_ERR_DEVICE, "internal: formula cell outside the table");
     if (!(fl & FX_FLAG_FULL)) break;
-    ncells <<= 2;   // a full hash table regrows and scatters again: no row is dropped
-    regrows++;
+    s.ncells <<= 2;   // no row is dropped
+    st.regrows++;
   }
-  const double scatter_ms = ms_since(t_start) - t_scatter0;
+  st.scatter_ms = ms_since(c.t_start) - s.t0;
+  st.mode = s.dense ? "dense" : "hash";
+  st.cells = s.dense ? cells.nkeys : s.ncells;
+  return s;
+}
 
+// Runs the program over every cell, compacts the rows that come out and fetches them with their sources.
+Joined evaluate_cells(const FxRun& c, CallCtx& X, const FxCall& call, const std::vector<FxOperand>& fo,
+                      const Scattered& sc, FxStats& st) {
+  hipStream_t stream = X.stream;
   FxEval V{};
-  V.T = T;
-  V.nops = prog.n;
-  V.has_group_bys = nk ? 1 : 0;
-  memcpy(V.ops, prog.ops, sizeof(FxOp) * size_t(prog.n));
-  for (int l = 0; l < L; l++) {
-    V.val[l] = fo[size_t(l)].val;
-    V.gid[l] = fo[size_t(l)].gid;
-    V.xform[l] = ops[size_t(l)].xform;
-    V.secs[l] = secs;
+  V.T = sc.T;
+  V.nops = call.prog.n;
+  V.has_group_bys = call.key_cols.empty() ? 0 : 1;
+  memcpy(V.ops, call.prog.ops, sizeof(FxOp) * size_t(call.prog.n));
+  for (size_t l = 0; l < fo.size(); l++) {
+    V.val[l] = fo[l].val;
+    V.gid[l] = fo[l].gid;
+    V.xform[l] = call.exprs[l].xform;
+    V.secs[l] = call.secs;
   }
-  const uint32_t nb = fx_blocks(ncells);
-  uint32_t* d_counts = static_cast<uint32_t*>(X->workspace("fx_counts", (size_t(nb) + 2) * 4));
-  if (!dense) {
-    uint32_t* bc = static_cast<uint32_t*>(X->workspace("fx_buckets", (size_t(nbuckets) * 2 + 2) * 4));
-    HIP_TRY(hipMemsetAsync(bc, 0, (size_t(nbuckets) * 2 + 2) * 4, st));
+  const uint32_t nb = fx_blocks(sc.ncells);
+  uint32_t* d_counts = static_cast<uint32_t*>(X.workspace("fx_counts", (size_t(nb) + 2) * 4));
+  if (!sc.dense) {
+    const size_t words = size_t(sc.T.nbuckets) * 2 + 2;
+    uint32_t* bc = static_cast<uint32_t*>(X.workspace("fx_buckets", words * 4));
+    HIP_TRY(hipMemsetAsync(bc, 0, words * 4, stream));
     V.bucket_count = bc;
-    V.bucket_cursor = bc + nbuckets + 1;
+    V.bucket_cursor = bc + sc.T.nbuckets + 1;
   }
-  HIP_TRY(launch_fx_eval_count(V, d_counts, st));
+  HIP_TRY(launch_fx_eval_count(V, d_counts, stream));
   uint32_t nout = 0;
-  HIP_TRY(hipMemcpyAsync(&nout, d_counts + nb, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  std::vector<int32_t> src_op(nout);
-  std::vector<uint32_t> src_gid(nout);
-  double eval_ms = 0, transfer_ms = 0;
-  if (nout) {
-    const size_t n = nout;
-    uint8_t* ob = static_cast<uint8_t*>(X->workspace("fx_out", n * 24 + 64));
-    int64_t* o_ts = reinterpret_cast<int64_t*>(ob);
-    double* o_val = reinterpret_cast<double*>(ob + n * 8);
-    int32_t* o_op = reinterpret_cast<int32_t*>(ob + n * 16);
-    uint32_t* o_gid = reinterpret_cast<uint32_t*>(ob + n * 20);
-    HIP_TRY(launch_fx_eval_write(V, d_counts, o_ts, o_val, o_op, o_gid, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    eval_ms = ms_since(t_start) - t_scatter0 - scatter_ms;
-    const double t1 = ms_since(t_start);
-    res->alloc_rows(n, false);
-    res->gid = nullptr;   // formula rows carry no group ids (lk_result_group_ids: NULL)
-    HIP_TRY(hipMemcpyAsync(res->ts, o_ts, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(res->val, o_val, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(src_op.data(), o_op, n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(src_gid.data(), o_gid, n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    transfer_ms = ms_since(t_start) - t1;
-  } else {
-    res->alloc_rows(0, false);
-    res->gid = nullptr;
+  HIP_TRY(hipMemcpyAsync(&nout, d_counts + nb, 4, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  const size_t n = nout;
+  Joined j{std::vector<int32_t>(n), std::vector<uint32_t>(n)};
+  st.out_rows = n;
+  if (!n) {
+    c.res->alloc_rows(0, false);
+    c.res->gid = nullptr;
+    return j;
   }
+  uint8_t* ob = static_cast<uint8_t*>(X.workspace("fx_out", n * 24 + 64));
+  int64_t* o_ts = reinterpret_cast<int64_t*>(ob);
+  double* o_val = reinterpret_cast<double*>(ob + n * 8);
+  int32_t* o_op = reinterpret_cast<int32_t*>(ob + n * 16);
+  uint32_t* o_gid = reinterpret_cast<uint32_t*>(ob + n * 20);
+  HIP_TRY(launch_fx_eval_write(V, d_counts, o_ts, o_val, o_op, o_gid, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  st.eval_ms = ms_since(c.t_start) - sc.t0 - st.scatter_ms;
+  const double t1 = ms_since(c.t_start);
+  c.res->alloc_rows(n, false);
+  c.res->gid = nullptr;   // formula rows carry no group ids (lk_result_group_ids: NULL)
+  HIP_TRY(hipMemcpyAsync(c.res->ts, o_ts, n * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(c.res->val, o_val, n * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(j.src_op.data(), o_op, n * 4, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(j.src_gid.data(), o_gid, n * 4, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  st.transfer_ms = ms_since(c.t_start) - t1;
+  return j;
+}
 
-  // ---- tags from (source operand, source group id); the operands' device rows are done with ----
-  for (Operand& o : ops) {
+// ---- tags from (source operand, source group id); the operands' device rows are done with ----
+void fill_tags(const std::vector<Operand>& ops, const Joined& j, lk_result* res) {
+  for (const Operand& o : ops) {
     if (o.res->dev_rows) (void)hipFree(o.res->dev_rows);
     o.res->dev_rows = nullptr;
   }
-  const size_t ncol = res->tag_names.size();
+  const size_t ncol = res->tag_names.size(), nout = j.src_op.size();
   // (an operand names a column twice when a queryTags key is also a groupBy: the row's own tag, else the queryTag)
   std::vector<std::vector<std::vector<size_t>>> col_of(ops.size(), std::vector<std::vector<size_t>>(ncol));
   for (size_t k = 0; k < ops.size(); k++)
@@ -690,19 +468,67 @@ int evaluate_formula(Engine& E, const std::string& json, int glob_size, bool dis
       for (size_t oc = 0; oc < tn.size(); oc++)
         if (tn[oc] == res->tag_names[c]) col_of[k][c].push_back(oc);
     }
-  res->ex_tags.assign(size_t(nout) * ncol, nullptr);
+  res->ex_tags.assign(nout * ncol, nullptr);
   for (size_t r = 0; r < nout; r++) {
-    const int32_t k = src_op[r];
-    if (k < 0 || k >= L) continue;   // a constant's empty tags
+    const int32_t k = j.src_op[r];
+    if (k < 0 || size_t(k) >= ops.size()) continue;   // a constant's empty tags
     const lk_result& orow = *ops[size_t(k)].res;
     for (size_t c = 0; c < ncol; c++)
       for (size_t oc : col_of[size_t(k)][c]) {
-        const char* v = orow.tag_of_gid(src_gid[r], oc);
+        const char* v = orow.tag_of_gid(j.src_gid[r], oc);
         if (v) res->ex_tags[r * ncol + c] = v;   // (a later column of the same name overwrites, as a tag map does)
       }
   }
-  for (Operand& o : ops) res->keep.push_back(o.res);   // the tag strings live in the operands' results
-  write_stats(dense ? "dense" : "hash", dense ? nkeys : ncells, regrows, scatter_ms, eval_ms, transfer_ms, nout);
+  for (const Operand& o : ops) res->keep.push_back(o.res);   // the tag strings live in the operands' results
+}
+
+}  // namespace
+
+// Distributed (lk_eval_formula_dist; DESIGN.md §7.6 "Distributed"): a rank is a pod.  Every operand is one sharded merged
+// evaluation whose rows land on rank 0 (kept on its device, or uploaded by it), the join runs on rank 0 alone.  comm_mu is
+// held for the whole call; the operands run in ascending byte order of their variable names, each closed by one
+// agreement of the ranks' outcomes, so every rank issues the same collectives and all fail at the same operand.
+// Everything decided before the first collective -- the parser, the gate, the shard check: fx_gate -- reads the request
+// alone.
+int evaluate_formula(Engine& E, const std::string& json, int glob_size, bool dist, lk_result* res) {
+  const FxRun c{E, res, std::chrono::steady_clock::now(), glob_size <= 0 ? 10 : glob_size, dist,
+                dist ? comm_world(E) : 1, dist ? comm_rank(E) : 0};
+  const FxCall call = fx_gate(json, dist, c.world, [&E](const std::string& pd) { return E.parse_cached(pd); });
+  FxStats st;
+  st.world = c.world, st.rank = c.rank;
+  res->exemplar = true;   // tags materialized per row (ex_tags): no bulk export of group ids
+  if (call.exprs.empty()) {   // no variable: no SketchGroup reaches the formula, no rows
+    write_stats(c, st);
+    return LK_OK;
+  }
+  if (dist && !E.comm) throw PlanError(LK_ERR_ARG, "lk_comm_init has not been called");
+  std::vector<Operand> ops(call.exprs.size());
+  for (size_t k = 0; k < ops.size(); k++) ops[k].x = &call.exprs[k];
+  run_operands(c, call, ops, st);
+  // Behind the last operand's last collective: from here a failure unwinds this rank alone.  The other ranks return
+  // their empty result; rank 0 looks at the rows for the first time.
+  st.kind = c.rank != 0 ? FxStats::OFF_ROOT : FxStats::ROOT;
+  if (c.rank != 0) {
+    write_stats(c, st);
+    return LK_OK;
+  }
+  place_rows(c, ops);
+  st.operands_ms = ms_since(c.t_start);
+  const RowSpan span = span_rows(ops, res);
+  st.operand_rows = span.total_rows;
+  if (!span.total_rows) {
+    write_stats(c, st);
+    return LK_OK;
+  }
+  std::vector<FxIdentity> ident;
+  const FxUnion un = union_space(E, call, ops, ident);
+  const FxCells cells = fx_cell_space(span.base, span.last, call.step, un.U);
+  CtxLease X(E);
+  const std::vector<FxOperand> fo = stage_operands(*X, ops, un, ident);
+  const Scattered sc = scatter(c, *X, call, fo, span, cells, un.U, st);
+  const Joined j = evaluate_cells(c, *X, call, fo, sc, st);
+  fill_tags(ops, j, res);
+  write_stats(c, st);
   return LK_OK;
 }
 

@@ -8,16 +8,9 @@
 
 namespace lk {
 
-constexpr int FX_MAXCOL = 8;                       // groupBy columns of a formula's key
 constexpr unsigned long long FX_EMPTY = ~0ull;     // an unclaimed leaf slot / hash key
-// Collapse ranks (smaller wins): a named row 2 * (its name's place in string order) + 4; a row without a name tag
-// sorts before every named row of its key unless one of its present groupBy tags sorts after the name tag; the one
-// all-absent row (queryTags) takes the odd rank between its neighbours (FxOperand::qt_rank).
-constexpr uint32_t FX_RANK_ABSENT = 0xffffffffu;   // name_rank entry of a dim id whose name tag is absent
-constexpr uint32_t FX_RANK_NONAME_FIRST = 1u;
-constexpr uint32_t FX_RANK_NONAME_LAST = 0xfffffffcu;
 enum FxFlag : uint32_t { FX_FLAG_FULL = 1u, FX_FLAG_OFFGRID = 2u, FX_FLAG_RANGE = 4u };
-enum FxXform : int { FX_XF_NONE = 0, FX_XF_MUL = 1, FX_XF_DIV = 2 };
+// (FX_MAXCOL, the collapse ranks FX_RANK_* and FxXform: formula_cell.hpp, which the host's HIP-free rules include)
 
 // The cell table: `nleaves` 64-bit slots per cell (name rank << 32 | row of the operand; FX_EMPTY: no row), dense
 // (cell = bucket * U + union group) or open addressing on that 64-bit key.
