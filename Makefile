@@ -54,8 +54,8 @@ $(RELIB): $(SRC)/regex.cpp $(SRC)/regex_capi.cpp $(SRC)/regex.hpp $(SRC)/unicode
 
 # host-only Java 17 number text, the field charts' text -> double classifier and the formula parser / cell function
 # (CPU differential tests); the filter planning (filter_plan.cpp) with the request parser, numeric literals and regex
-# compiler it calls; the numeric groupBys' rules over agreed data (numgroup_agree.cpp)
-TX_SRCS = $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/formula_join.cpp $(SRC)/formula_join_sim.cpp $(SRC)/ex_select_sim.cpp $(SRC)/bucket_sim.cpp $(SRC)/clu_sim.cpp $(SRC)/filter_plan.cpp $(SRC)/filter_plan_sim.cpp $(SRC)/plan.cpp $(SRC)/numleaf.cpp $(SRC)/regex.cpp $(SRC)/numgroup_agree.cpp
+# compiler it calls; the numeric groupBys' rules over agreed data (numgroup_agree.cpp); the host DDSketch (ddsketch.cpp)
+TX_SRCS = $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/formula_join.cpp $(SRC)/formula_join_sim.cpp $(SRC)/ex_select_sim.cpp $(SRC)/bucket_sim.cpp $(SRC)/clu_sim.cpp $(SRC)/ddsketch.cpp $(SRC)/ddsketch_sim.cpp $(SRC)/filter_plan.cpp $(SRC)/filter_plan_sim.cpp $(SRC)/plan.cpp $(SRC)/numleaf.cpp $(SRC)/regex.cpp $(SRC)/numgroup_agree.cpp
 $(TXLIB): $(TX_SRCS) $(HDRS)
 	g++ $(CXXFLAGS_HOST) -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -shared -o $@ $(TX_SRCS)
 

@@ -108,6 +108,19 @@ uint32_t lk_clu_sub_sim(uint32_t nrows, const uint32_t* sb, uint32_t nsb, uint32
 int lk_clu_count_sim(uint32_t nrows, const uint16_t* rows, uint32_t n, const uint32_t* sb, uint32_t nsb, int use_sub,
                      uint32_t* cnt);
 
+/* Drives the host DDSketch (lakeside_amd/csrc/ddsketch.cpp, dd::Sketch: the sketches of the metrics percentiles and the
+ * assembly of the kernels' bins) with nothing restated.  Sketch A: accept over vals[0..n) in order, then add_bin over the
+ * n_bins pairs (bins[i] = a kernel bin id of layout.hpp, below DD_NBINS; counts[i]); sketch B likewise from the m*
+ * arguments; A.merge(B).  *rejected = the position of the first value accept refused (NaN, a magnitude beyond the
+ * mapping's range), counted over vals then mvals, or -1: nothing after a refused value is fed and B is not merged.
+ * Writes quantiles[i] = A.quantile(qs[i]), *total = A.count() and, where non-NULL, consts[0..8) = gamma, multiplier,
+ * relative_accuracy, min_indexable, max_indexable, DD_BIAS, DD_HALF, DD_NBINS.  A.serialize() goes to out; returns its
+ * length, -1 for a bin id outside the key space, -5 when cap is too small. */
+long lk_dd_sim(const double* vals, size_t n, const uint32_t* bins, const double* counts, size_t n_bins,
+               const double* mvals, size_t mn, const uint32_t* mbins, const double* mcounts, size_t mn_bins,
+               const double* qs, size_t nq, double* quantiles, long* rejected, double* consts, double* total,
+               uint8_t* out, size_t cap);
+
 /* Plans the filter of a PushDownRequest as the evaluator does before it reads a segment (lakeside_amd/csrc/
  * filter_plan.cpp: the leaf loop of the shape gate, plan_filter, plan_truth); numeric_group_bys[0..n) are the groupBys
  * to take as columns stored as numbers (the evaluator learns them from the loaded files).  Writes a JSON object into out
