@@ -41,8 +41,8 @@ $(OBJDIR)/%.o: $(SRC)/%.hip $(DEV_HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(SCAN_TILES): $(SRC)/scan_kernel.hpp
-$(SCAN_LEAN): $(SRC)/scan_kernel.hpp $(SRC)/lean_kernel.hpp
+$(SCAN_TILES): $(SRC)/scan_kernel.hpp $(SRC)/vleaf.hpp
+$(SCAN_LEAN): $(SRC)/scan_kernel.hpp $(SRC)/vleaf.hpp $(SRC)/lean_kernel.hpp
 $(SCAN_CLU): $(SRC)/clu_kernel.hpp
 
 $(LIB): $(HOST_OBJS) $(HIP_OBJS)

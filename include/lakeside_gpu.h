@@ -94,7 +94,14 @@ int lk_engine_drop_caches(lk_engine* e);
  * push_down_json: PushDownRequest.toJson wire format (core/.../model/SegmentRequest.scala:30-60).
  * paths[i]: cache key (or local file, loaded on a miss) of segmentRequests[i].
  * glob_size: 10 for local Parquet, 5 for remote (Commons.scala:361); 0 = 10.
- * flags: LK_PER_GLOB_ROWS or LK_MERGED. */
+ * flags: LK_PER_GLOB_ROWS or LK_MERGED.
+ * Numeric comparison leaves (gt / ge / lt / le) in a `p<NN>` or `ces` chart are evaluated when every one of them reads
+ * the chart's value column and sits in a conjunct of numeric leaves only (at most 5 of them, 6 leaves in all): "p99 of
+ * the requests slower than 250 ms".  A row whose value is NULL then fails the filter, and a NaN or infinite value the
+ * leaves drop does not reach the sketch.  Any other numeric leaf in such a chart -- on another column, in a conjunct
+ * with string leaves, beside a groupBy over a column stored as a number, or under `ces` over metrics -- is
+ * LK_ERR_UNSUPPORTED ("numeric comparison leaves in sketch queries"), decided from the request before a segment is
+ * read (the groupBy case: from the loaded files' schemas; in lk_eval_pushdown_dist on every rank alike). */
 int lk_eval_pushdown(lk_engine* e, const char* push_down_json, const char* const* paths, size_t n_paths,
                      int glob_size, unsigned flags, lk_result** out);
 

@@ -132,6 +132,17 @@ long lk_dd_sim(const double* vals, size_t n, const uint32_t* bins, const double*
  * evaluator does. */
 int lk_filter_plan_sim(const char* request_json, const char* const* numeric_group_bys, size_t n, char* out, size_t cap);
 
+/* Numeric comparison leaves on a chart's value column (`value > 250`), as the fused kernels test them per passing row
+ * (lakeside_amd/csrc/vleaf.hpp, vleaf_pass over QParams::vl / vtab as the evaluator fills them).  Plans the request as
+ * the evaluator does before it reads a segment -- the shape's aggregate and leaf loop, the gate's rule for p<NN> / ces
+ * charts (numeric leaves only as value leaves), plan_filter, plan_truth -- then tests the n values (valid[i] == 0: a NULL,
+ * vals[i] ignored).  Returns 0 with *vleaf = the plan's vleaf (the value leaves are tested apart from the string
+ * conjuncts) and, when it is 1, pass[i] = the value leaves' conjuncts are TRUE for value i (0 everywhere otherwise); or
+ * a PlanError's code (the gate's LK_ERR_UNSUPPORTED -2 among them) with its message in msg (NUL-terminated; empty when
+ * cap is too small).  Reads LK_NO_VLEAF as the evaluator does. */
+int lk_vleaf_sim(const char* request_json, const uint8_t* valid, const double* vals, size_t n, int* vleaf,
+                 uint8_t* pass, char* msg, size_t cap);
+
 /* Numeric groupBys, the two rules the ranks of a distributed evaluation apply to agreed data (lakeside_amd/csrc/
  * numgroup_agree.cpp; the evaluator calls the same functions, sharded or not).
  * Classes.  A (groupBy column, glob) travels as 3 bytes per rank: a VARCHAR file, a BOOLEAN file, the largest value rank

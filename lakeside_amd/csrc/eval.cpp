@@ -355,12 +355,13 @@ void setup_scan(const EvalCall& C, const Plan& pl, DevState& dv) {
   if (dv.P.split_ok && getenv("LK_NO_CLU_AGG")) dv.P.split_ok |= SPLIT_OK_NO_CLU_AGG;
   // LK_NO_CLU_SUB=1 (read per call, independent of the above): scan_clu streams its split tiles' ranges whole
   if (dv.P.split_ok && getenv("LK_NO_CLU_SUB")) dv.P.split_ok |= SPLIT_OK_NO_CLU_SUB;
-  if (pl.fp.vleaf && !pl.sg.qsegs.empty()) {   // scan_lean tests the value leaves of every row its string conjuncts pass
+  // scan_lean (and, in COUNT / p<NN> / ces calls, scan_tiles) tests the value leaves of every row its string conjuncts pass
+  if (pl.fp.vleaf && !pl.sg.qsegs.empty()) {
     dv.P.nvl = uint32_t(pl.fp.nleaves.size());
     dv.P.vtab = pl.fp.vtab;
     for (size_t k = 0; k < pl.fp.nleaves.size(); k++) {
       const NumLeaf& nl = pl.fp.nleaves[k];
-      dv.P.vl[k] = VLeaf{nl.dlo, nl.dhi, nl.lo_incl, nl.hi_incl, nl.nan_pass, 0u};
+      dv.P.vl[k] = vleaf_of(nl);
     }
   }
   // scan_lean: a dense table whose group space fits LDS for the few buckets a tile spans is aggregated in the tile's
@@ -1392,6 +1393,7 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   stage("tables");
   plan_cells(C, pl.qs, pl.fp, pl.gp, pl.dp, pl.cs);
   plan_truth(C, pl.qs, pl.fp);
+  sketch_leaf_check(pl.qs, pl.fp);   // (a numeric groupBy found in the files: the value leaves' route is gone)
   plan_segments(C, pl.qs, pl.fp, pl.gp, pl.cs, pl.sg);
   stage("qsegs");
   plan_table_mode(pl.qs, pl.sg, pl.cs);

@@ -181,29 +181,7 @@ void shape_gate(const EvalCall& C, QueryShape& qs) {
   if (qs.fchart && C.R.is_tag_query) throw PlanError(LK_ERR_UNSUPPORTED, "field chart: a tag query takes no chart field");
   if (C.R.dataset != "logs" && C.R.dataset != "traces" && C.R.dataset != "metrics")
     throw PlanError(LK_ERR_ARG, "Invalid dataset: " + C.R.dataset);
-  if (qs.tagq) qs.agg = AGG_ROWS;
-  // Cardinality (`ces` in the chart's rollup, PushDownAggregatorStage.scala:44,82-94; computeCardinality sets it,
-  // QueryEngineV2.scala:616-617): per step one HLL over the rows' group-key strings, whatever the SQL aggregate.
-  // Metrics: `ces` as the chart's aggregation compiles to `SELECT ts, 1.0 as value, name, <groupBys> ... WHERE
-  // <filter>` -- every passing row, no rollup column (BaseExpr.scala:385-388); a metrics rollup of "ces" under another
-  // aggregation stays that aggregation over rollup_ces (the SQL reads that column).
-  else if (C.R.aggregation == "ces" || (C.R.rollup.find("ces") != std::string::npos && C.R.dataset != "metrics")) qs.agg = AGG_CES;
-  else if (C.R.aggregation == "sum") qs.agg = AGG_SUM;
-  else if (C.R.aggregation == "min") qs.agg = AGG_MIN;
-  else if (C.R.aggregation == "max") qs.agg = AGG_MAX;
-  else if (C.R.aggregation == "count") qs.agg = AGG_COUNT;
-  else if (C.R.aggregation == "avg") qs.agg = AGG_AVG;
-  else if (C.R.aggregation.size() > 1 && C.R.aggregation[0] == 'p' && C.R.dataset != "metrics") qs.agg = AGG_SKETCH;
-  else throw PlanError(LK_ERR_UNSUPPORTED, "aggregation " + C.R.aggregation + " (sketch path) is not on the hot path");
-  // Percentiles (logs / traces): BaseExpr.getChartSql selects the passing rows (BaseExpr.scala:397-399), the
-  // worker's PushDownAggregatorStage builds one DDSketch per (step, group-key tags) (PushDownAggregatorStage.scala:
-  // 69-81, 188-197), query-api merges per (timestamp, tags) and reads getValueAtQuantile(p / 100)
-  // (BaseExpr.scala:59-61).  Here: the scan bins every value on the GPU (COUNT per (cell, DDSketch bin)), the host
-  // assembles the sketches.
-  qs.sketch = qs.agg == AGG_SKETCH;
-  qs.ces = qs.agg == AGG_CES;
-  // queries whose SQL references no value column: tag queries (COUNT(*)) and metrics `ces` (1.0 per row)
-  qs.no_value_col = qs.tagq || (qs.ces && C.R.dataset == "metrics");
+  shape_aggregation(C.R, qs);   // agg, sketch, ces, no_value_col (filter_plan.cpp)
   // Field chart (chart.fieldName / fieldType): the same scan over `<fieldName>$<fieldType>` (field_chart_gate)
   qs.fscale = qs.fchart ? field_chart_gate(C.R, qs.agg, qs.per_glob_rows) : 0.0;
   if (qs.sketch) {
@@ -223,7 +201,9 @@ void shape_gate(const EvalCall& C, QueryShape& qs) {
   qs.vcol = value_column(C.R);
 
   shape_leaves(C.R, qs);   // the filter's leaves, its numeric columns (filter_plan.cpp)
-  if (qs.numeric && (qs.sketch || qs.ces)) throw PlanError(LK_ERR_UNSUPPORTED, "numeric comparison leaves in sketch queries");
+  // p<NN> / ces: numeric leaves run only as value leaves -- decided from a scratch plan of the request's filter, so the
+  // refusal still reads the request and the shape alone and comes before a segment is loaded or a collective issued
+  sketch_leaf_gate(C.R, qs);
   // (distributed: the numeric leaves' per-glob decisions -- a bad literal, a VARCHAR column -- come from the agreed glob
   // unions, and the general row scan's partial tables reduce like any other)
 }
@@ -897,8 +877,10 @@ void plan_segments(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp
         }
         if (seg_lean && !S.cols[cn].pages_lean_name) seg_lean = false;
       }
-      // vleaf: only scan_lean tests the value leaves -- a segment it does not take whole goes to the general row scan
-      if (fp.vleaf && (!seg_lean || !fp.vleaf_shape)) general = true;
+      // vleaf: only scan_lean tests the value leaves -- a segment it does not take whole goes to the general row scan.
+      // Not in p<NN> / ces calls: their scan_tiles (the COUNT instantiations) tests the leaves too, so the segment stays
+      // fused -- p<NN>: scan_tiles takes every tile; ces: scan_lean the lean tiles, scan_tiles the rest
+      if (fp.vleaf && (!seg_lean || !fp.vleaf_shape) && !(qs.sketch || qs.ces)) general = true;
       if (!general) sg.all_lean = sg.all_lean && seg_lean;
       // scan_clu takes the segment whole: its copy was built from these two columns, covers every tile, and every
       // tile that meets the window is pinned or split (clu.hpp) -- no other kernel then runs over the segment

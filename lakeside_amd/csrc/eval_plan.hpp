@@ -87,6 +87,7 @@ struct QueryShape {
   std::vector<const FilterNode*> all_leaves;
   std::vector<std::string> nums;   // numeric query columns: the filter's, then the numeric groupBys not among them
   bool numeric = false;
+  bool num_leaves = false;         // the filter holds gt / ge / lt / le leaves (numeric: or a numeric groupBy)
   // groupBys over columns stored as numbers (plan_numeric_group_bys): numeric group dimensions, DESIGN §7.7
   std::vector<std::string> numgbs;
   int numgb_index(const std::string& name) const {
@@ -101,7 +102,8 @@ struct FilterPlan : LeafNumbering {
   std::vector<std::string> gbs;    // the groupBys, once each
   std::vector<uint8_t> bad_regex;  // per leaf: a pattern RE2 rejects
   // truth tables (plan_truth)
-  bool vleaf = false;              // numeric leaves on the value column alone, tested by scan_lean per passing row
+  bool vleaf = false;              // numeric leaves on the value column alone, tested per passing row (scan_lean; in
+                                   //   COUNT / p<NN> / ces calls scan_tiles too)
   uint32_t vtab = 0;
   std::vector<uint32_t> truth, truth_early, truth_late, truth_x;   // truth_x: the general row scan's (vleaf)
   uint32_t late_mask = 0;
@@ -293,9 +295,17 @@ void plan_table_mode(const QueryShape& qs, const SegPlan& sg, CellSpace& cs);
 // hash-mode table keeps every segment on the other kernels.
 void plan_cluster(const CellSpace& cs, SegPlan& sg);
 
+// A value leaf as the fused kernels read it (QParams::vl; vleaf.hpp states the test).
+inline VLeaf vleaf_of(const NumLeaf& nl) { return VLeaf{nl.dlo, nl.dhi, nl.lo_incl, nl.hi_incl, nl.nan_pass, 0u}; }
+
 // The pure part of the filter planning (filter_plan.cpp: the request and the shape alone, no Engine, no HIP call):
 // shape_gate's leaf loop (all_leaves, nums, numeric), and what plan_filter / plan_truth do for a call.
 void shape_leaves(const Request& R, QueryShape& qs);
+void shape_aggregation(const Request& R, QueryShape& qs);   // agg, sketch, ces, no_value_col (qs.tagq is set)
+// p<NN> / ces charts take numeric leaves only as value leaves (FilterPlan::vleaf); LK_ERR_UNSUPPORTED otherwise.  The
+// gate plans a scratch filter from the request alone; the check reads the call's own plan (after plan_truth).
+void sketch_leaf_gate(const Request& R, const QueryShape& qs);
+void sketch_leaf_check(const QueryShape& qs, const FilterPlan& fp);
 void plan_filter(const Request& R, const QueryShape& qs, FilterPlan& fp);
 void plan_truth(const Request& R, const QueryShape& qs, FilterPlan& fp);
 

@@ -109,6 +109,64 @@ void shape_leaves(const Request& R, QueryShape& qs) {
       throw PlanError(LK_ERR_ARG, "Invalid operator " + l->op);
   }
   qs.numeric = !qs.nums.empty();
+  qs.num_leaves = qs.numeric;   // (numeric groupBys make a shape numeric later; the sketch gate asks about leaves)
+}
+
+// The aggregate a chart asks for; qs.tagq is set.
+// Cardinality (`ces` in the chart's rollup, PushDownAggregatorStage.scala:44,82-94; computeCardinality sets it,
+// QueryEngineV2.scala:616-617): per step one HLL over the rows' group-key strings, whatever the SQL aggregate.
+// Metrics: `ces` as the chart's aggregation compiles to `SELECT ts, 1.0 as value, name, <groupBys> ... WHERE
+// <filter>` -- every passing row, no rollup column (BaseExpr.scala:385-388); a metrics rollup of "ces" under another
+// aggregation stays that aggregation over rollup_ces (the SQL reads that column).
+void shape_aggregation(const Request& R, QueryShape& qs) {
+  if (qs.tagq) qs.agg = AGG_ROWS;
+  else if (R.aggregation == "ces" || (R.rollup.find("ces") != std::string::npos && R.dataset != "metrics")) qs.agg = AGG_CES;
+  else if (R.aggregation == "sum") qs.agg = AGG_SUM;
+  else if (R.aggregation == "min") qs.agg = AGG_MIN;
+  else if (R.aggregation == "max") qs.agg = AGG_MAX;
+  else if (R.aggregation == "count") qs.agg = AGG_COUNT;
+  else if (R.aggregation == "avg") qs.agg = AGG_AVG;
+  else if (R.aggregation.size() > 1 && R.aggregation[0] == 'p' && R.dataset != "metrics") qs.agg = AGG_SKETCH;
+  else throw PlanError(LK_ERR_UNSUPPORTED, "aggregation " + R.aggregation + " (sketch path) is not on the hot path");
+  // Percentiles (logs / traces): BaseExpr.getChartSql selects the passing rows (BaseExpr.scala:397-399), the
+  // worker's PushDownAggregatorStage builds one DDSketch per (step, group-key tags) (PushDownAggregatorStage.scala:
+  // 69-81, 188-197), query-api merges per (timestamp, tags) and reads getValueAtQuantile(p / 100)
+  // (BaseExpr.scala:59-61).  Here: the scan bins every value on the GPU (COUNT per (cell, DDSketch bin)), the host
+  // assembles the sketches.
+  qs.sketch = qs.agg == AGG_SKETCH;
+  qs.ces = qs.agg == AGG_CES;
+  // queries whose SQL references no value column: tag queries (COUNT(*)) and metrics `ces` (1.0 per row)
+  qs.no_value_col = qs.tagq || (qs.ces && R.dataset == "metrics");
+}
+
+// Numeric comparison leaves in p<NN> / ces charts.  The reference compiles them into the row-selecting SQL's WHERE like
+// any other leaf (BaseExpr.scala:397-399 with 488-498); here the sketch routes take them only as value leaves
+// (FilterPlan::vleaf: every numeric leaf on the chart's value column, in conjuncts of their own, <= VLEAF_MAX of them
+// and <= TT_MAX_LEAVES leaves in all), which scan_tiles, scan_lean and ex_scan all test.  Every other one is refused --
+// a leaf on another column, a mixed conjunct, LK_NO_VLEAF=1, metrics `ces` (no value column is bound) -- and so is a
+// filter the planner itself refuses, under this text, which came first before the gate read the plan.  Reads the
+// request and the shape alone: every rank of a distributed call decides alike, before its first collective.
+static const char* const kSketchLeafRefusal = "numeric comparison leaves in sketch queries";
+void sketch_leaf_gate(const Request& R, const QueryShape& qs) {
+  if (!qs.num_leaves || !(qs.sketch || qs.ces)) return;
+  bool ok = !qs.no_value_col;
+  if (ok) {
+    try {
+      FilterPlan fp;
+      plan_filter(R, qs, fp);
+      plan_truth(R, qs, fp);
+      ok = fp.vleaf;
+    } catch (const PlanError&) {
+      ok = false;
+    }
+  }
+  if (!ok) throw PlanError(LK_ERR_UNSUPPORTED, kSketchLeafRefusal);
+}
+// The same rule on the call's own plan: a groupBy the loaded files store as a number joins the numeric columns after
+// the gate (plan_numeric_group_bys) and takes the value leaves' route away (in a distributed call from agreed classes:
+// every rank refuses alike).
+void sketch_leaf_check(const QueryShape& qs, const FilterPlan& fp) {
+  if (qs.num_leaves && (qs.sketch || qs.ces) && !fp.vleaf) throw PlanError(LK_ERR_UNSUPPORTED, kSketchLeafRefusal);
 }
 
 void plan_filter(const Request& R, const QueryShape& qs, FilterPlan& fp) {

@@ -1,6 +1,7 @@
 // Host-only test hook (include/lakeside_text.h): the filter planning of filter_plan.cpp for one request, in the order
 // evaluate_once runs it -- the shape's leaf loop, the numeric groupBys as plan_numeric_group_bys leaves them,
-// plan_filter, plan_truth -- written out as JSON.
+// plan_filter, plan_truth -- written out as JSON (lk_filter_plan_sim); and the value leaves' rule of vleaf.hpp over the
+// plan of a request that passed the shape gate's rule for p<NN> / ces charts (lk_vleaf_sim).
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -8,6 +9,7 @@
 #include "../../include/lakeside_text.h"
 #include "eval_plan.hpp"
 #include "hostutil.hpp"
+#include "vleaf.hpp"
 
 namespace {
 std::string hex_words(const std::vector<uint32_t>& w) {
@@ -77,6 +79,38 @@ extern "C" int lk_filter_plan_sim(const char* request_json, const char* const* n
     return rc == LK_ERR_MEMORY ? e.code : rc;
   } catch (const std::exception& e) {
     (void)put(e.what(), LK_ERR_ARG, out, cap);
+    return LK_ERR_ARG;
+  }
+}
+
+extern "C" int lk_vleaf_sim(const char* request_json, const uint8_t* valid, const double* vals, size_t n, int* vleaf,
+                            uint8_t* pass, char* msg, size_t cap) {
+  using namespace lk;
+  if (msg && cap) msg[0] = 0;
+  try {
+    const Request R = parse_request(request_json);
+    QueryShape qs;   // shape_gate's steps that the filter planning reads
+    qs.tagq = R.is_tag_query && !R.tag_name.empty();
+    shape_aggregation(R, qs);
+    qs.metrics = R.dataset == "metrics" && !qs.tagq;
+    qs.vcol = value_column(R);
+    shape_leaves(R, qs);
+    sketch_leaf_gate(R, qs);
+    FilterPlan fp;
+    plan_filter(R, qs, fp);
+    plan_truth(R, qs, fp);
+    sketch_leaf_check(qs, fp);
+    if (vleaf) *vleaf = fp.vleaf ? 1 : 0;
+    VLeaf vl[VLEAF_MAX] = {};
+    const uint32_t nvl = fp.vleaf ? uint32_t(fp.nleaves.size()) : 0u;   // setup_scan fills QParams::vl the same way
+    for (uint32_t k = 0; k < nvl; k++) vl[k] = vleaf_of(fp.nleaves[k]);
+    for (size_t i = 0; i < n && pass; i++) pass[i] = fp.vleaf ? uint8_t(vleaf_pass(vl, nvl, fp.vtab, valid[i] != 0, vals[i])) : 0;
+    return LK_OK;
+  } catch (const PlanError& e) {
+    (void)put(e.what(), e.code, msg, cap);
+    return e.code;
+  } catch (const std::exception& e) {
+    (void)put(e.what(), LK_ERR_ARG, msg, cap);
     return LK_ERR_ARG;
   }
 }

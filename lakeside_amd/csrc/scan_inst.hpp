@@ -51,6 +51,33 @@ void launch_lean(const QParams& P, dim3 grid, hipStream_t st) {
 template <int AGG, bool HASH>
 void launch_tiles(const QParams& P, dim3 grid, hipStream_t st) {
   const dim3 block(BLOCK);
+  // Value leaves in a COUNT / p<NN> / ces call (QParams::nvl; the filter then has a truth table: plan_truth): the VLEAF
+  // instantiations, which load the value and test it per listed row.  Every other call launches the leaf-free code.
+  if constexpr (AGG == AGG_COUNT) {
+    if (P.nvl && P.truth) {
+      if (P.lean && P.nstr >= 2) {   // the SLIM LDS layout, as below
+        switch (P.nstr) {
+          case 2: hipLaunchKernelGGL((scan_tiles<AGG, 2, true, HASH, true, true>), grid, block, 0, st, P); return;
+          case 3: hipLaunchKernelGGL((scan_tiles<AGG, 3, true, HASH, true, true>), grid, block, 0, st, P); return;
+          case 4: hipLaunchKernelGGL((scan_tiles<AGG, 4, true, HASH, true, true>), grid, block, 0, st, P); return;
+          case 5: hipLaunchKernelGGL((scan_tiles<AGG, 5, true, HASH, true, true>), grid, block, 0, st, P); return;
+          case 6: hipLaunchKernelGGL((scan_tiles<AGG, 6, true, HASH, true, true>), grid, block, 0, st, P); return;
+          case 7: hipLaunchKernelGGL((scan_tiles<AGG, 7, true, HASH, true, true>), grid, block, 0, st, P); return;
+          default: hipLaunchKernelGGL((scan_tiles<AGG, 8, true, HASH, true, true>), grid, block, 0, st, P); return;
+        }
+      }
+      switch (P.nstr) {
+        case 1: hipLaunchKernelGGL((scan_tiles<AGG, 1, true, HASH, false, true>), grid, block, 0, st, P); return;
+        case 2: hipLaunchKernelGGL((scan_tiles<AGG, 2, true, HASH, false, true>), grid, block, 0, st, P); return;
+        case 3: hipLaunchKernelGGL((scan_tiles<AGG, 3, true, HASH, false, true>), grid, block, 0, st, P); return;
+        case 4: hipLaunchKernelGGL((scan_tiles<AGG, 4, true, HASH, false, true>), grid, block, 0, st, P); return;
+        case 5: hipLaunchKernelGGL((scan_tiles<AGG, 5, true, HASH, false, true>), grid, block, 0, st, P); return;
+        case 6: hipLaunchKernelGGL((scan_tiles<AGG, 6, true, HASH, false, true>), grid, block, 0, st, P); return;
+        case 7: hipLaunchKernelGGL((scan_tiles<AGG, 7, true, HASH, false, true>), grid, block, 0, st, P); return;
+        default: hipLaunchKernelGGL((scan_tiles<AGG, 8, true, HASH, false, true>), grid, block, 0, st, P); return;
+      }
+    }
+  }
   if (!P.truth) {   // > TT_MAX_LEAVES leaves: one generic instantiation interprets the Kleene program per row
     hipLaunchKernelGGL((scan_tiles<AGG, MAXSTR, false, HASH>), grid, block, 0, st, P);
     return;

@@ -24,6 +24,7 @@
 
 #include "bucket.hpp"
 #include "device_common.hpp"
+#include "vleaf.hpp"
 
 namespace lk {
 
@@ -316,7 +317,7 @@ struct ChunkT {
   uint32_t n;      // listed rows in the chunk (uniform; 0: none)
 };
 
-template <int AGG, int NSTR, bool TT, bool HASH, bool SLIM = false>
+template <int AGG, int NSTR, bool TT, bool HASH, bool SLIM = false, bool VLEAF = false>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NSTR == 1 ? 4 : (NSTR <= 3 ? 3 : 2)))) void scan_tiles(QParams P) {
   __shared__ Lds<NSTR, SLIM> L;
   constexpr int HS = hslots_v<NSTR, SLIM>;
@@ -562,6 +563,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NSTR == 1
   }
   const bool one_bucket = tile_b >= 0;
   const bool sketch = AGG == AGG_COUNT && P.sketch != 0u;   // uniform
+  // Value leaves (COUNT, p<NN> and ces calls with QParams::nvl set): instantiations of their own, picked on the host
+  // (launch_tiles) -- inside the leaf-free kernels the test cost the NSTR = 7 ones 28 to 40 B of scratch
+  constexpr bool vleaf = AGG == AGG_COUNT && VLEAF;
 
   Acc acc;
   acc_reset<AGG>(acc, EMPTY);
@@ -603,7 +607,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NSTR == 1
         ch.ts[j] = __builtin_amdgcn_raw_buffer_load_b64(rs0, live ? (vb0 + tv) * 8u : OOB, 0, 0);
         if (count_plan) pbytes += 128u * new_lines(live, (vb0 + tv) * 8u, last_ts_line);
       }
-      if (AGG != AGG_COUNT || sketch) {
+      if (AGG != AGG_COUNT || sketch || vleaf) {   // (ces reads a value only for its leaves)
         ch.v[j] = __builtin_amdgcn_raw_buffer_load_b64(rs1, vok ? (vb1 + vv) * 8u : OOB, 0, 0);
         if (count_plan) pbytes += 128u * new_lines(vok, (vb1 + vv) * 8u, last_v_line);
       }
@@ -628,7 +632,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NSTR == 1
       ch.ts[0] = __builtin_amdgcn_raw_buffer_load_b64(rs0, live ? (vb0 + tv) * 8u : OOB, 0, 0);
       if (count_plan) pbytes += 128u * new_lines(live, (vb0 + tv) * 8u, last_ts_line);
     }
-    if (AGG != AGG_COUNT || sketch) {
+    if (AGG != AGG_COUNT || sketch || vleaf) {
       ch.v[0] = __builtin_amdgcn_raw_buffer_load_b64(rs1, vok ? (vb1 + vv) * 8u : OOB, 0, 0);
       if (count_plan) pbytes += 128u * new_lines(vok, (vb1 + vv) * 8u, last_v_line);
     }
@@ -675,6 +679,13 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(NSTR == 1
       unsigned long long cell = (glob_base + (unsigned long long)b) * P.ngroups + ch.gid[j];
       const double v = __longlong_as_double((long long)(((uint64_t)ch.v[j].y << 32) | ch.v[j].x));
       bool vvalid = (ch.vok >> j) & 1u;
+      if constexpr (vleaf) {   // numeric leaves on the value column: COUNT, p<NN> and ces charts
+        // Before dd_bin: a NaN / inf / NULL the leaves drop never reaches the sketch (no FLAG_SKETCH_RANGE, no zero bin).
+        // The bounds are read through the kernarg segment pointer (P is the kernel's only argument): a runtime index
+        // into the by-value argument would copy it to scratch (scan_lean's row does the same)
+        const VLeaf* vls = static_cast<const QParams*>((const void*)__builtin_amdgcn_kernarg_segment_ptr())->vl;
+        if (!vleaf_pass(vls, P.nvl, P.vtab, vvalid, v)) continue;
+      }
       if constexpr (AGG == AGG_COUNT) {
         if (sketch) {   // DDSketch bin of the value (NULL: 0.0, counted); every passing row counts
           cell = cell * DD_NBINS + dd_bin(P, vvalid ? v : 0.0);
