@@ -13,7 +13,7 @@ SYNTH   = lakeside_amd/liblakeside_synth.so
 RELIB   = lakeside_amd/liblakeside_regex.so
 TXLIB   = lakeside_amd/liblakeside_text.so
 
-HOST_SRCS = $(SRC)/numgroup_agree.cpp $(SRC)/numleaf.cpp $(SRC)/exemplar.cpp $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/formula_join.cpp $(SRC)/formula_eval.cpp $(SRC)/ddsketch.cpp $(SRC)/hll.cpp $(SRC)/regex.cpp $(SRC)/codec.cpp $(SRC)/parquet.cpp $(SRC)/plan.cpp $(SRC)/loader.cpp $(SRC)/engine.cpp $(SRC)/filter_plan.cpp $(SRC)/eval_plan.cpp $(SRC)/eval.cpp $(SRC)/eval_rows.cpp $(SRC)/eval_compose.cpp $(SRC)/dims.cpp $(SRC)/comm.cpp $(SRC)/abi.cpp
+HOST_SRCS = $(SRC)/numgroup_agree.cpp $(SRC)/numleaf.cpp $(SRC)/exemplar.cpp $(SRC)/tagnames.cpp $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/formula_join.cpp $(SRC)/formula_eval.cpp $(SRC)/ddsketch.cpp $(SRC)/hll.cpp $(SRC)/regex.cpp $(SRC)/codec.cpp $(SRC)/parquet.cpp $(SRC)/plan.cpp $(SRC)/loader.cpp $(SRC)/engine.cpp $(SRC)/filter_plan.cpp $(SRC)/eval_plan.cpp $(SRC)/eval.cpp $(SRC)/eval_rows.cpp $(SRC)/eval_compose.cpp $(SRC)/dims.cpp $(SRC)/comm.cpp $(SRC)/abi.cpp
 HOST_OBJS = $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(HOST_SRCS))
 # the fused scan kernels: one unit per (aggregate, kernel family, table mode) so they compile in parallel
 SCAN_LEAN  = $(foreach a,sum min max count,$(foreach m,d h,$(OBJDIR)/scan_$(a)_lean_$(m).o))
@@ -55,7 +55,7 @@ $(RELIB): $(SRC)/regex.cpp $(SRC)/regex_capi.cpp $(SRC)/regex.hpp $(SRC)/unicode
 # host-only Java 17 number text, the field charts' text -> double classifier and the formula parser / cell function
 # (CPU differential tests); the filter planning (filter_plan.cpp) with the request parser, numeric literals and regex
 # compiler it calls; the numeric groupBys' rules over agreed data (numgroup_agree.cpp); the host DDSketch (ddsketch.cpp)
-TX_SRCS = $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/formula_join.cpp $(SRC)/formula_join_sim.cpp $(SRC)/ex_select_sim.cpp $(SRC)/bucket_sim.cpp $(SRC)/clu_sim.cpp $(SRC)/ddsketch.cpp $(SRC)/ddsketch_sim.cpp $(SRC)/filter_plan.cpp $(SRC)/filter_plan_sim.cpp $(SRC)/plan.cpp $(SRC)/numleaf.cpp $(SRC)/regex.cpp $(SRC)/numgroup_agree.cpp
+TX_SRCS = $(SRC)/jdtoa.cpp $(SRC)/fieldnum.cpp $(SRC)/formula.cpp $(SRC)/formula_join.cpp $(SRC)/formula_join_sim.cpp $(SRC)/tagnames_sim.cpp $(SRC)/ex_select_sim.cpp $(SRC)/bucket_sim.cpp $(SRC)/clu_sim.cpp $(SRC)/ddsketch.cpp $(SRC)/ddsketch_sim.cpp $(SRC)/filter_plan.cpp $(SRC)/filter_plan_sim.cpp $(SRC)/plan.cpp $(SRC)/numleaf.cpp $(SRC)/regex.cpp $(SRC)/numgroup_agree.cpp
 $(TXLIB): $(TX_SRCS) $(HDRS)
 	g++ $(CXXFLAGS_HOST) -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ -shared -o $@ $(TX_SRCS)
 

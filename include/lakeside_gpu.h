@@ -101,7 +101,25 @@ int lk_engine_drop_caches(lk_engine* e);
  * leaves drop does not reach the sketch.  Any other numeric leaf in such a chart -- on another column, in a conjunct
  * with string leaves, beside a groupBy over a column stored as a number, or under `ces` over metrics -- is
  * LK_ERR_UNSUPPORTED ("numeric comparison leaves in sketch queries"), decided from the request before a segment is
- * read (the groupBy case: from the loaded files' schemas; in lk_eval_pushdown_dist on every rank alike). */
+ * read (the groupBy case: from the loaded files' schemas; in lk_eval_pushdown_dist on every rank alike).
+ * Tag-name queries -- isTagQuery without a tagDataType, no chart, processor.tagNameCompressionEnabled = true (what
+ * POST /api/v1/tags/{dataset} without a tagName sends, QueryEngineV2.scala:419-491) -- return every tag name once: the
+ * worker's SELECT * rows (Commons.scala:428-459) after TagNameCompressionStage.  A glob's union schema (files in list
+ * order, columns in file order, first appearance fixes the place) must start with "_cardinalhq.timestamp"; a row is
+ * (timestamp, getDouble of the union's second column with NULL as 0.0, tags = the later columns whose text is non-NULL,
+ * non-empty and not "null"), and a tag is kept only on the first row of the call that carries its name.  Two
+ * deterministic stand-ins replace what the reference leaves to timing: rows of a glob count in file-list order and, within
+ * a file, in row order (DuckDB's default preserve_insertion_order; assumed), and the seen-set the reference shares among
+ * concurrently running globs sees the globs in request order.  Rows come back in ascending timestamp order (descending
+ * under reverseSort), ties by glob, file position and row; LK_PER_GLOB_ROWS and LK_MERGED return the same rows, the
+ * glob column being the row's glob or 0.  Tags are per row: lk_result_tag_value answers NULL for a column that is not
+ * among the row's new names, lk_result_group_ids returns NULL and lk_result_num_group_columns 0.  lk_result_stats
+ * carries "tag_names": {"columns", "found", "rows", "tiles_walked", "tiles_pruned"}.  LK_ERR_UNSUPPORTED, the message
+ * beginning "tag queries without a tagDataType: ": processor.tagNameCompressionEnabled absent or false (the reference
+ * then streams every passing row), processor.resetValueToField, extract / compute, a chart, a glob whose first column
+ * is not the timestamp (the reference emits such rows whole under the wall clock), a second column that is VARCHAR /
+ * BOOLEAN or of different numeric types in one glob, and lk_eval_pushdown_dist; a column of the files that is not loaded
+ * fails the call as any referenced unloaded column does. */
 int lk_eval_pushdown(lk_engine* e, const char* push_down_json, const char* const* paths, size_t n_paths,
                      int glob_size, unsigned flags, lk_result** out);
 

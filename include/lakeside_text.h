@@ -161,6 +161,18 @@ int lk_numgroup_classes_sim(const uint8_t* classes, size_t n_ranks, int* union_t
 long lk_numgroup_values_sim(const int32_t* union_types, const uint64_t* keys, const size_t* counts, size_t n_ranks,
                             uint32_t* ids, char* out, size_t cap);
 
+/* Tag-name queries (isTagQuery without a tagDataType; include/lakeside_gpu.h), the host-only rules
+ * (lakeside_amd/csrc/tagnames.hpp, as the evaluator calls them).
+ * lk_tagnames_gate_sim: what the call decides from the request and the globs' schemas alone.  schemas_json: per glob,
+ * per readable file in list order, the file's columns in file order as [name, Parquet physical type].  dist != 0: the
+ * call is lk_eval_pushdown_dist.  Returns 0 with {"unions": [the glob's union_by_name column order]} in out, or the
+ * refusal's code (LK_ERR_ARG -1, LK_ERR_UNSUPPORTED -2) with its message in out; -5 when cap is too small.
+ * lk_tagnames_rows_sim: the fold of the per-column first keys first[0..n) (all ones: the column has none) into the
+ * emitted rows: keys[i] = the i-th distinct key ascending, row_of_col[k] = the row that carries column k as a tag
+ * (0xffffffff: none).  Returns the rows, or -5 when they exceed cap. */
+int lk_tagnames_gate_sim(const char* request_json, const char* schemas_json, int dist, char* out, size_t cap);
+long lk_tagnames_rows_sim(const uint64_t* first, size_t n, uint64_t* keys, uint32_t* row_of_col, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

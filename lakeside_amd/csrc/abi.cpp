@@ -271,7 +271,7 @@ const char* lk_result_tag_value(const lk_result* r, size_t row, size_t col) {
   if (!r || row >= r->nrows || col >= r->tag_names.size()) return nullptr;
   return r->tag(row, col);
 }
-const uint32_t* lk_result_group_ids(const lk_result* r) { return r ? r->gid : nullptr; }
+const uint32_t* lk_result_group_ids(const lk_result* r) { return (r && !r->no_group_ids) ? r->gid : nullptr; }
 size_t lk_result_num_group_columns(const lk_result* r) { return (r && !r->exemplar) ? r->tcols.size() : 0; }
 const char* const* lk_result_tag_dictionary(const lk_result* r, size_t col, uint64_t* stride, uint64_t* ndim) {
   if (stride) *stride = 1;

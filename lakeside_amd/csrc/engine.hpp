@@ -376,6 +376,7 @@ struct lk_result {
   // exemplar rows: every row's tag strings, materialized ([row][tag column]; nullptr: tag absent)
   bool exemplar = false;
   std::vector<const char*> ex_tags;
+  bool no_group_ids = false;   // tag-name rows: lk_result_group_ids answers NULL (tags are read per row)
 
   const char* tag(size_t row, size_t col) const {
     if (exemplar) return ex_tags[row * tag_names.size() + col];

@@ -1353,6 +1353,10 @@ static int evaluate_once(Engine& E, const std::shared_ptr<const Request>& Rp, co
   // Exemplar query (no chart, not a tag query): raw rows, ORDER BY timestamp LIMIT n (BaseExpr.scala:234-239)
   if (!R.is_tag_query && !R.has_chart)
     return evaluate_exemplar(E, *X, R, paths, n_paths, glob_size, flags, dist, res, std::string(), shard);
+  // Tag-name query (isTagQuery without a tagDataType): SELECT * ... WHERE <filter> (BaseExpr.scala:231-232), each tag
+  // name once (tagnames.cpp)
+  if (R.is_tag_query && R.tag_name.empty())
+    return evaluate_tagnames(E, *X, R, paths, n_paths, glob_size, flags, dist, res);
 
   const EvalCall C{E, *X, R, paths, n_paths, glob_size, flags, shard, dist, redo, res, t_start};
   Plan pl;   // owns the segments and the FieldTab lock until the call returns

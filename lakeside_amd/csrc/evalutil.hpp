@@ -65,6 +65,9 @@ double ms_since(std::chrono::steady_clock::time_point t0);
 int evaluate_exemplar(Engine& E, CallCtx& X, const Request& R, const char* const* paths, size_t n_paths,
                       int glob_size, unsigned flags, bool dist, lk_result* res, const std::string& numtag = std::string(),
                       const int32_t* shard = nullptr);
+// Tag-name queries (isTagQuery without a tagDataType): tagnames.cpp.  Local calls only (dist: LK_ERR_UNSUPPORTED).
+int evaluate_tagnames(Engine& E, CallCtx& X, const Request& R, const char* const* paths, size_t n_paths, int glob_size,
+                      unsigned flags, bool dist, lk_result* res);
 // Numeric comparison leaves (numleaf.cpp): gt / ge / lt / le; the normalized literal (PlanError(LK_ERR_ARG) where the
 // reference's SQL fails); the leaf's interval on numeric filter column `col`.
 bool numeric_op(const std::string& op);

@@ -150,9 +150,11 @@ __device__ __forceinline__ void ex_merge(const QParams& q, unsigned long long ce
 }
 
 // NDM 0: HIST / EMIT / TAGNUM / AGG by X.mode.  1: NUMDIM.  2: AGG with numeric group dimensions.  (Instantiations of
-// their own: the numeric-dimension state costs the other modes no register.)
+// their own: the numeric-dimension state costs the other modes no register.)  3: MASK (tag names): the rows EMIT would
+// list, as one pass bit per row and a pass count per tile.
 template <int NDM>
 __device__ __forceinline__ void ex_scan_body(const XParams& X) {
+  constexpr bool ND = NDM == 1 || NDM == 2;   // the numeric group columns are read
   // column state by query column: 0 timestamp, 1 value (AGG), 2 .. 2+nstr strings, then numeric filter columns
   __shared__ XHot H[MAXQCOL];
   __shared__ LRun vr[MAXQCOL][RUN_CAP];
@@ -167,7 +169,7 @@ __device__ __forceinline__ void ex_scan_body(const XParams& X) {
   const uint32_t g = Sp->glob_slot;
   const bool aggm = NDM == 2 || (NDM == 0 && X.mode == XMODE_AGG);
   const bool swin = aggm || NDM == 1;   // the glob window of the segment descriptor (NUMDIM: the aggregate scan's rows)
-  const uint32_t rg = NDM ? X.seg_glob[blockIdx.y] : 0u;   // the segment's glob, whatever the cell space shares
+  const uint32_t rg = ND ? X.seg_glob[blockIdx.y] : 0u;   // the segment's glob, whatever the cell space shares
   const int64_t lo = swin ? Sp->win_lo : X.rlo[g], hi = swin ? Sp->win_hi : X.rhi[g];
   const TileDesc* tdp = Sp->tiles + t;
   if (lo >= hi || tdp->ts_max < lo || tdp->ts_min >= hi) return;   // zone map outside the glob's open range
@@ -293,7 +295,7 @@ __device__ __forceinline__ void ex_scan_body(const XParams& X) {
       if (qc < 2 || qc >= 2 + ns) {   // PLAIN numeric: timestamp, value, numeric filter column
         const bool w8 = h.kind == PAGE_PLAIN64;
         // BOOLEAN: a numeric tag or a numeric group column only
-        const bool bl = h.kind == PAGE_BOOL && (uint32_t(qc) == X.tag_qc || (NDM && ((X.ndmask >> qc) & 1u)));
+        const bool bl = h.kind == PAGE_BOOL && (uint32_t(qc) == X.tag_qc || (ND && ((X.ndmask >> qc) & 1u)));
         if (!w8 && h.kind != PAGE_PLAIN32 && !bl) ok = false;
         // (BOOLEAN: bit-packed bytes read as whole dwords -- the slack keeps the stream's last dword in range)
         const __amdgpu_buffer_rsrc_t rs = make_rsrc(h.vals, h.vals_len + (bl ? 4u : 0u));
@@ -310,7 +312,7 @@ __device__ __forceinline__ void ex_scan_body(const XParams& X) {
           tag_raw = raw;
           tag_ok = ok;
         }
-        if (NDM) {
+        if (ND) {
 #pragma unroll
           for (int k = 0; k < MAXND; k++)
             if (k < int(X.nnd) && uint32_t(qc) == X.nd[k].qc) {
@@ -525,6 +527,15 @@ __device__ __forceinline__ void ex_scan_body(const XParams& X) {
           X.out[2 * size_t(base) + 1] = ((unsigned long long)blockIdx.y << 48) | ((unsigned long long)t << 16) | r;
         }
       }
+    } else if (NDM == 3) {
+      // the wave's 64 rows as one word of the tile's bitmap (rows past the tile's end never pass: ts_ok is false)
+      const unsigned long long m = __ballot(pass);
+      const uint32_t w0 = c0 + uint32_t(wave) * 64u;
+      if (lane == 0 && w0 < nrows) {
+        const uint32_t ti = Sp->tile_begin + t;
+        X.mask[size_t(X.mask_off[ti]) + (w0 >> 6)] = m;
+        if (m) atomicAdd(&X.pass_cnt[ti], uint32_t(__popcll(m)));
+      }
     }
   }
   if (NDM == 1) {   // flush: one device CAS per distinct key of the tile
@@ -548,6 +559,7 @@ __device__ __forceinline__ void ex_scan_body(const XParams& X) {
 __global__ __launch_bounds__(BLOCK) void ex_scan(XParams X) { ex_scan_body<0>(X); }
 __global__ __launch_bounds__(BLOCK) void ex_scan_discover(XParams X) { ex_scan_body<1>(X); }
 __global__ __launch_bounds__(BLOCK) void ex_scan_numdim(XParams X) { ex_scan_body<2>(X); }
+__global__ __launch_bounds__(BLOCK) void ex_scan_mask(XParams X) { ex_scan_body<3>(X); }
 
 __global__ __launch_bounds__(256) void tag_compact(const unsigned long long* keys, const unsigned long long* cnt,
                                                    unsigned long long n, unsigned long long tcap,
@@ -666,6 +678,133 @@ __global__ __launch_bounds__(256) void ex_gather(GParams G) {
   }
   G.val[i] = v;
   G.ok[i] = 1;
+}
+
+// Tag names: one workgroup per (tile, column of the call's union, segment of the launch's group).  first[k] is the
+// smallest key found so far for column k; a workgroup whose tile lies wholly above it has nothing to add and returns,
+// so with tiles dispatched in ascending order (x fastest, segments slowest) a column costs little once it is found.
+// Otherwise the tile's rows are walked 256 at a time: pass bit (ex_scan_mask's bitmap), definition level (the def-run
+// lookup and wave prefix ex_scan uses, which also gives a string row its value index), and for a string column the
+// dictionary id of its code against the ids of "" and "null".  The first hit of the step -- by ballot per wave, the
+// smallest of the waves -- goes into first[k] with one 64-bit atomicMin and the walk stops.  A tile whose def runs are
+// all RLE zero (all NULL), or whose value runs are all RLE runs of an excluded id, is left before the walk.
+__global__ __launch_bounds__(BLOCK) void col_first(TnParams P) {
+  __shared__ LRun vr[RUN_CAP];
+  __shared__ LRun dr[RUN_CAP];
+  __shared__ uint32_t wsum[BLOCK / 64];
+  __shared__ uint32_t whit[BLOCK / 64];
+  __shared__ unsigned long long cur;
+
+  const uint32_t t = blockIdx.x, k = blockIdx.y, s = P.seg0 + blockIdx.z;
+  const QSeg* Sp = P.segs + s;
+  if (t >= Sp->ntiles) return;
+  const TnCol& C = P.cols[size_t(s) * P.ncols + k];
+  if (!C.present) return;
+  const uint32_t ti = Sp->tile_begin + t;
+  if (P.pass_cnt[ti] == 0u) return;   // no passing row (or outside the glob window: ex_scan_mask wrote nothing)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned long long key0 = ((unsigned long long)s << 48) | ((unsigned long long)t << 16);
+  // one thread reads first[k] for the workgroup (other workgroups lower it meanwhile: the decision must be uniform)
+  if (tid == 0) cur = __hip_atomic_load(&P.first[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  if (cur < key0) {
+    if (tid == 0) atomicAdd(&P.stats[1], 1ull);
+    return;
+  }
+  if (tid == 0) atomicAdd(&P.stats[0], 1ull);
+
+  const TileCol tc = C.tcols[t];
+  const uint32_t nrows = Sp->tiles[t].nrows;
+  const bool dict = tc.kind == PAGE_DICT;
+  if (!dict && tc.kind != PAGE_PLAIN64 && tc.kind != PAGE_PLAIN32 && tc.kind != PAGE_BOOL) return;
+  const uint32_t nruns = dict ? (tc.nruns < RUN_CAP ? tc.nruns : RUN_CAP) : 0u;
+  const uint32_t ndruns = tc.has_nulls ? (tc.ndruns < RUN_CAP ? tc.ndruns : RUN_CAP) : 0u;
+  if (dict && nruns == 0u) return;   // no value in this tile: every row NULL
+  int dlive = 0, vlive = 0;          // a run that can hold a keepable row
+  for (uint32_t i = tid; i < nruns; i += BLOCK) {
+    const RunDesc r = C.runs[tc.run_lo + i];
+    vr[i] = LRun{r.start, r.off_lit, r.value};
+    if (r.off_lit & 0x80000000u) {
+      vlive = 1;
+    } else if (r.value < tc.dict_n) {
+      const uint32_t gl = C.remap[tc.remap + r.value];
+      vlive |= int(gl != C.id_empty && gl != C.id_null);
+    }
+  }
+  for (uint32_t i = tid; i < ndruns; i += BLOCK) {
+    const RunDesc r = C.runs[tc.drun_lo + i];
+    dr[i] = LRun{r.start, r.off_lit, r.value};
+    dlive |= int((r.off_lit & 0x80000000u) != 0u || r.value != 0u);
+  }
+  // (also the barrier behind the staging) the tile is left when no def run or no value run can hold a keepable row
+  const int any_d = __syncthreads_or(dlive), any_v = __syncthreads_or(vlive);
+  if ((ndruns && !any_d) || (dict && !any_v)) return;
+
+  const __amdgpu_buffer_rsrc_t drs = make_rsrc(C.base + tc.defs, tc.defs_len + 8);
+  const __amdgpu_buffer_rsrc_t vrs = make_rsrc(C.base + tc.vals, tc.vals_len + 8);
+  const unsigned long long* mw = P.mask + P.mask_off[ti];
+  uint32_t carry = 0;
+  for (uint32_t c0 = 0; c0 < nrows; c0 += BLOCK) {
+    const uint32_t r = c0 + uint32_t(tid);
+    const bool inb = r < nrows;
+    const bool pass = inb && ((mw[r >> 6] >> (r & 63u)) & 1ull);
+    bool ok = inb;
+    uint32_t vi = tc.vbase + r;
+    if (ndruns) {   // block-uniform
+      const uint32_t row = tc.row_in_page + r;
+      const int ri = find_run(dr, int(ndruns), row);
+      const bool bit = inb && (hybrid_get_buf(drs, dr[ri], row, 1) & 1u);
+      const unsigned long long m = __ballot(bit);
+      const uint32_t below = lanes_below(m);
+      if (lane == 0) wsum[wave] = uint32_t(__popcll(m));
+      __syncthreads();
+      uint32_t before = 0, all = 0;
+#pragma unroll
+      for (int w = 0; w < BLOCK / 64; w++) {
+        before += w < wave ? wsum[w] : 0u;
+        all += wsum[w];
+      }
+      vi = tc.vbase + carry + before + below;
+      carry += all;
+      ok = bit;
+    }
+    bool hit = pass && ok;
+    if (dict && hit) {
+      const int ri = find_run(vr, int(nruns), vi);
+      const uint32_t idx = hybrid_get_buf(vrs, vr[ri], vi, int(tc.bw));
+      hit = false;
+      if (idx < tc.dict_n) {
+        const uint32_t gl = C.remap[tc.remap + idx];
+        hit = gl != C.id_empty && gl != C.id_null;
+      }
+    }
+    const unsigned long long hm = __ballot(hit);
+    if (lane == 0) whit[wave] = hm ? c0 + uint32_t(wave) * 64u + uint32_t(__ffsll((long long)hm) - 1) : ~0u;
+    __syncthreads();
+    uint32_t best = ~0u;
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; w++) best = whit[w] < best ? whit[w] : best;
+    __syncthreads();   // wsum / whit are written again by the next step
+    if (best != ~0u) {
+      if (tid == 0) atomicMin(&P.first[k], key0 | best);
+      break;
+    }
+  }
+}
+
+hipError_t launch_ex_scan_mask(const XParams& X, hipStream_t stream) {
+  if (!X.nsegs || !X.max_tiles) return hipSuccess;
+  if (!X.mask || !X.mask_off || !X.pass_cnt) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ex_scan_mask, dim3(X.max_tiles, X.nsegs), dim3(BLOCK), 0, stream, X);
+  return hipGetLastError();
+}
+
+hipError_t launch_col_first(const TnParams& P, hipStream_t stream) {
+  if (!P.nsegs || !P.max_tiles || !P.ncols) return hipSuccess;
+  if (P.ncols > 65535u || P.nsegs > 65535u || !P.mask || !P.mask_off || !P.pass_cnt || !P.first || !P.stats)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(col_first, dim3(P.max_tiles, P.ncols, P.nsegs), dim3(BLOCK), 0, stream, P);
+  return hipGetLastError();
 }
 
 hipError_t launch_ex_scan(const XParams& X, hipStream_t stream) {

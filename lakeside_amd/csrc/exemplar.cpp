@@ -42,6 +42,7 @@
 #include "eval_plan.hpp"
 #include "evalutil.hpp"
 #include "ex_select.hpp"
+#include "exemplar.hpp"
 #include "hostutil.hpp"
 #include "kernels.hpp"
 #include "layout.hpp"
@@ -100,112 +101,11 @@ std::vector<Row> sum_first_seen(std::vector<Row>& rows, Key key, Add add) {
   return out;
 }
 
-// A pinned host block from the engine's pool for the length of a transfer (returned to the pool on scope exit).
-struct PinnedTmp {
-  HostBlock b;
-  explicit PinnedTmp(size_t n) : b(pinned_acquire(n)) {}
-  ~PinnedTmp() { pinned_release(b); }
-  PinnedTmp(const PinnedTmp&) = delete;
-  PinnedTmp& operator=(const PinnedTmp&) = delete;
-  void* p() const { return b.p; }
-};
-
-// What the request asks for: depends on the request and flags alone.
-struct XShape {
-  bool tagnum = false, logs = false, desc = true, per_glob_rows = false;
-  uint64_t limit = 0;
-  std::string numtag;
-  std::vector<const FilterNode*> all_leaves;
-  std::vector<std::string> nums;   // numeric comparison columns (gt/ge/lt/le, BaseExpr.scala:488-498)
-  // numeric tag: its leaves (query-api's `exists` on the tag) are numeric IS NOT NULL leaves; the tag column is a
-  // numeric column of the scan either way
-  bool num_col(const FilterNode* l) const { return numeric_op(l->op) || (tagnum && l->k == numtag); }
-};
-
-// The filter columns (string dictionaries) and the Kleene program.
-struct XFilter : LeafNumbering {
-  std::vector<LeafCol> strs;
-};
-
-struct XGlob : XSel {
-  std::vector<int> segs;
-  bool skip = false;
-  uint32_t leaf_false = 0;
-  std::vector<std::string> cols;          // output columns: projection, then the union (file order)
-  std::map<std::string, int> types;       // union type per column
-  int type_or(const std::string& name, int dflt) const {
-    const auto it = types.find(name);
-    return it == types.end() ? dflt : it->second;
-  }
-};
-
-struct XGlobs {
-  std::vector<std::shared_ptr<Segment>> segs;
-  std::vector<uint8_t> seg_bad;
-  std::vector<XGlob> globs;
-};
-
-// Per-segment descriptors: `qsegs` goes to the device as it is, `meta` runs parallel to it.
-struct XSegMeta {
-  const Segment* seg;
-  uint32_t pos;    // segment position in the glob
-  uint32_t glob;
-};
-struct XSegs {
-  std::vector<QSeg> qsegs;
-  std::vector<XSegMeta> meta;
-  uint64_t rows_scanned = 0;
-  uint32_t max_tiles = 0;
-};
-
-// The per-glob range words of the staged block, [4][ng]: a HIST pass reads all four, TAGNUM and EMIT the range only.
-struct XRanges {
-  int64_t* w = nullptr;
-  size_t ng = 0;
-  int64_t& rlo(size_t g) const { return w[g]; }
-  int64_t& rhi(size_t g) const { return w[ng + g]; }
-  int64_t& hbase(size_t g) const { return w[2 * ng + g]; }
-  int64_t& hwidth(size_t g) const { return w[3 * ng + g]; }
-  void range(size_t g, bool live, int64_t lo, int64_t hi) const {
-    rlo(g) = live ? lo : 0;
-    rhi(g) = live ? hi : 0;
-  }
-};
-
-// The query staged for the device: one pinned block and its device copy, the scan parameters pointing into it.
-struct XDev {
-  hipStream_t st = nullptr;
-  uint8_t *hbuf = nullptr, *dbuf = nullptr;
-  size_t stage_bytes = 0, o_rng = 0, o_n = 0;
-  XRanges rng;                 // host side
-  uint32_t* hist = nullptr;    // host side: the histogram read back each pass
-  uint32_t* d_hist = nullptr;
-  XParams P{};
-  float scan_ms = 0.f;
-  // the scan between the two events, its time added to scan_ms once the caller has synchronized
-  void scan(CallCtx& X) {
-    HIP_TRY(hipEventRecord(X.ev_scan0, st));
-    HIP_TRY(launch_ex_scan(P, st));
-    HIP_TRY(hipEventRecord(X.ev_scan1, st));
-  }
-  void scanned(CallCtx& X) {
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, X.ev_scan0, X.ev_scan1));
-    scan_ms += ms;
-  }
-};
-
-struct Cand {
-  int64_t ts;
-  uint32_t qseg;
-  uint32_t pos;       // segment position in the glob
-  uint64_t row;       // row in the file
-  unsigned long long ref;
-};
+}  // namespace
 
 // ---- the stages, in call order ----
 
-XShape x_gate(const EvalCall& C, const std::string& numtag) {
+static XShape x_gate(const EvalCall& C, const std::string& numtag) {
   const Request& R = C.R;
   XShape qs;
   qs.numtag = numtag;
@@ -228,6 +128,12 @@ XShape x_gate(const EvalCall& C, const std::string& numtag) {
   qs.limit = qs.tagnum ? 0 : uint64_t(R.limit);
   qs.per_glob_rows = (C.flags & LK_PER_GLOB_ROWS) != 0;
 
+  x_leaves(R, qs);
+  return qs;
+}
+
+void x_leaves(const Request& R, XShape& qs) {
+  const std::string& numtag = qs.numtag;
   collect_leaves(R.filter.get(), qs.all_leaves);
   for (auto* l : qs.all_leaves) {
     if (l->extracted || l->computed) throw PlanError(LK_ERR_UNSUPPORTED, "extracted/computed filter fields");
@@ -242,7 +148,6 @@ XShape x_gate(const EvalCall& C, const std::string& numtag) {
       throw PlanError(LK_ERR_ARG, "Invalid operator " + l->op);
   }
   if (qs.tagnum && std::find(qs.nums.begin(), qs.nums.end(), numtag) == qs.nums.end()) qs.nums.push_back(numtag);
-  return qs;
 }
 
 // No segments: Commons.scala:393-396, the sentinel DataPoint(-1, -1, {}).
@@ -299,7 +204,8 @@ XGlobs x_globs(const EvalCall& C, const XShape& qs, const XFilter& fp) {
       gp.seg_bad[i] = 1;
     }
   }
-  const std::vector<std::string> proj = qs.tagnum ? std::vector<std::string>{kTimestamp, numtag}
+  const std::vector<std::string> proj = qs.star ? std::vector<std::string>{}
+                                       : qs.tagnum ? std::vector<std::string>{kTimestamp, numtag}
                                        : qs.logs ? std::vector<std::string>{kTimestamp, kValue, kName, kMessage}
                                                  : std::vector<std::string>{kTimestamp, kValue, kSpanName, kSpanKind};
   const std::set<std::string> fset = field_set(R);
@@ -359,7 +265,7 @@ std::vector<std::vector<uint32_t>> x_tables(Engine& E, const XFilter& fp) {
 }
 
 // Query column qc of q = S's column `name`, when S has it.
-void bind_col(QSeg& q, int qc, const Segment& S, const std::string& name, bool want_string, const XShape& qs,
+static void bind_col(QSeg& q, int qc, const Segment& S, const std::string& name, bool want_string, const XShape& qs,
               const XFilter& fp, const XGlob& g) {
   const int c = S.col_index(name);
   if (c < 0) return;
@@ -496,6 +402,8 @@ XDev x_stage(const EvalCall& C, const XShape& qs, const XFilter& fp, const std::
   P.tag_qc = ~0u;
   return D;
 }
+
+namespace {
 
 // ---- tag query over a numeric tag: SELECT "<tag>", COUNT(*) ... GROUP BY "<tag>" per glob (BaseExpr.scala:127-138):
 // one TAGNUM pass counts passing rows per (glob, canonical tag value); the host prints each value as JDBC getString
@@ -756,12 +664,8 @@ std::vector<const Cand*> order_and_fold(const EvalCall& C, const XShape& qs, siz
   return stream;
 }
 
-// Every output column of the selected rows: raw values [nsel][ncols] and their non-NULL flags.
-struct XGathered {
-  std::vector<std::string> out_cols;
-  std::vector<unsigned long long> val;
-  std::vector<uint8_t> ok;
-};
+}  // namespace
+
 XGathered gather_columns(const EvalCall& C, const XGlobs& gp, const XSegs& sg, hipStream_t st,
                          const std::vector<const Cand*>& stream) {
   XGathered G;
@@ -811,16 +715,22 @@ XGathered gather_columns(const EvalCall& C, const XGlobs& gp, const XSegs& sg, h
   return G;
 }
 
-// Rows: timestamp, getDouble(value) (SQL NULL -> 0.0), tags as JDBC getString text.
+// Rows: timestamp, getDouble(value column) (SQL NULL -> 0.0), tags as JDBC getString text.
 void write_rows(const EvalCall& C, const XGlobs& gp, const XSegs& sg, const std::vector<const Cand*>& stream,
-                const XGathered& G) {
+                const XGathered& G, bool second_col, const std::vector<uint8_t>* keep) {
   lk_result* res = C.res;
   const std::vector<std::string>& out_cols = G.out_cols;
   const size_t nsel = stream.size(), ncols = out_cols.size(), nq = sg.qsegs.size();
   res->alloc_rows(nsel);
   res->tag_names = out_cols;
   res->ex_tags.assign(nsel * ncols, nullptr);
-  const size_t vcol = size_t(std::find(out_cols.begin(), out_cols.end(), std::string(kValue)) - out_cols.begin());
+  // the value column per glob: "_cardinalhq.value", or the glob's second column (SELECT *)
+  std::vector<size_t> vcol(gp.globs.size(), ncols);
+  for (size_t gi = 0; gi < gp.globs.size(); gi++) {
+    const std::vector<std::string>& gc = gp.globs[gi].cols;
+    if (second_col && gc.size() < 2) continue;
+    vcol[gi] = size_t(std::find(out_cols.begin(), out_cols.end(), second_col ? gc[1] : std::string(kValue)) - out_cols.begin());
+  }
   for (size_t i = 0; i < nsel; i++) {
     res->ts[i] = stream[i]->ts;
     res->glob[i] = sg.meta[stream[i]->qseg].glob;
@@ -852,7 +762,8 @@ void write_rows(const EvalCall& C, const XGlobs& gp, const XSegs& sg, const std:
       const uint32_t q = stream[i]->qseg;
       const HostCol& hc = *qcol[q];
       const unsigned long long raw = G.val[i * ncols + k];
-      if (k == vcol) res->val[i] = raw_as_double(raw, hc.ptype);
+      if (k == vcol[sg.meta[q].glob]) res->val[i] = raw_as_double(raw, hc.ptype);
+      if (keep && !(*keep)[i * ncols + k]) continue;
       if (hc.is_string) {
         if (qut[q] != pq::BYTE_ARRAY) throw PlanError(LK_ERR_UNSUPPORTED, "union_by_name over string and numeric " + name);
         const std::string& s = (*gd)[size_t(raw)];
@@ -864,6 +775,8 @@ void write_rows(const EvalCall& C, const XGlobs& gp, const XSegs& sg, const std:
     }
   }
 }
+
+namespace {
 
 // This process's segments; the time in ex_scan goes to *scan_ms too (the distributed call's stats).
 void exemplar_local(const EvalCall& C, const std::string& numtag, double* scan_ms) {

@@ -214,7 +214,43 @@ struct XParams {
   const uint32_t* ndids;           // AGG: dim id per slot
   uint32_t* ndones;                // [glob][nnd]: NUMDIM: all-ones key seen; AGG: its dim id
   uint32_t* ndflags;               // NUMDIM: FLAG_HASH_FULL
+  // ex_scan_mask (tag names): tile t of segment S is tile S.tile_begin + t of the call; its pass bits start at word
+  // mask_off[tile] of `mask` (one bit per row, 64 rows per word), its passing rows are counted in pass_cnt[tile]
+  unsigned long long* mask;
+  const uint32_t* mask_off;
+  uint32_t* pass_cnt;
 };
+// The pass mask of every row of X.segs (tag names): window and filter evaluated per row exactly as EMIT evaluates
+// them, in an instantiation of its own (ex_scan_body<3>); per 64 rows one ballot word into `mask`, its popcount added
+// to the tile's pass_cnt; nothing else is written.  A tile outside its glob's range writes nothing: its count stays 0.
+hipError_t launch_ex_scan_mask(const XParams& X, hipStream_t stream);
+
+// col_first (tag names): per column of the call's union the smallest key (segment << 48 | tile << 16 | row, segments
+// staged in glob and file order) of a row whose pass bit is set and whose value is keepable -- non-NULL and, for a
+// string column, neither "" nor "null" (the column dictionary's ids of the two; TN_NO_ID: the dictionary holds none).
+struct TnCol {                     // one (segment, union column)
+  const uint8_t* base;             // segment streams
+  const RunDesc* runs;
+  const TileCol* tcols;
+  const uint32_t* remap;
+  uint32_t present;                // 0: absent from the segment, or not a tag column of the segment's glob (U[0], U[1])
+  uint32_t id_empty, id_null;
+  uint32_t pad;
+};
+constexpr uint32_t TN_NO_ID = ~0u;
+struct TnParams {
+  const QSeg* segs;                // the call's segments (tile_begin set)
+  uint32_t seg0, nsegs;            // this launch's group of them
+  uint32_t max_tiles;              // of the group
+  uint32_t ncols;
+  const TnCol* cols;               // [call segment][ncols]
+  const unsigned long long* mask;  // as XParams, written by ex_scan_mask over the same group
+  const uint32_t* mask_off;
+  const uint32_t* pass_cnt;
+  unsigned long long* first;       // [ncols], all ones: none yet (64-bit atomicMin)
+  unsigned long long* stats;       // [0]: workgroups that opened their tile; [1]: pruned by first[]
+};
+hipError_t launch_col_first(const TnParams& P, hipStream_t stream);
 // TAGNUM tables -> records [key, count, glob] of the occupied slots (unordered); count at *out_n.
 hipError_t launch_tag_compact(const unsigned long long* keys, const unsigned long long* cnt, unsigned long long tcap,
                               uint32_t nglobs, unsigned long long* out, uint32_t* out_n, hipStream_t stream);

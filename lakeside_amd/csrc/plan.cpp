@@ -104,6 +104,11 @@ Request parse_request(const std::string& text) {
     if (const Json* n = td->get("tagName"); n && n->is_str()) r.tag_name = n->str;
     if (const Json* d = td->get("dataType"); d && d->is_str()) r.tag_data_type = d->str;
   }
+  if (const Json* pr = p.get("processor"); pr && pr->is_obj()) {   // PostPushDownProcessor
+    if (const Json* x = pr->get("tagNameCompressionEnabled"); x && x->kind == Json::Bool) r.tag_name_compression = x->b;
+    if (const Json* x = pr->get("resetValueToField"); x && !x->is_null())
+      r.reset_value_to_field = x->is_str() ? x->str : x->scalar_text();
+  }
   if (const Json* x = p.get("reverseSort"); x && x->kind == Json::Bool) r.reverse_sort = x->b;
   const Json* segs = p.get("segmentRequests");
   if (!segs || !segs->is_arr()) throw PlanError(LK_ERR_ARG, "missing segmentRequests");
@@ -221,6 +226,8 @@ Request copy_request(const Request& r) {
   c.reverse_sort = r.reverse_sort;
   c.tag_name = r.tag_name;
   c.tag_data_type = r.tag_data_type;
+  c.tag_name_compression = r.tag_name_compression;
+  c.reset_value_to_field = r.reset_value_to_field;
   c.segments = r.segments;
   return c;
 }

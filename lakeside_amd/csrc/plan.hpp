@@ -60,6 +60,9 @@ struct Request {
   std::string order = "DESC";
   bool is_tag_query = false, reverse_sort = false;
   std::string tag_name, tag_data_type = "string";   // PushDownRequest.tagDataType (SegmentRequest.scala:55-58)
+  // PushDownRequest.processor (PostPushDownProcessor, SegmentRequest.scala:26): tag-name queries set the first
+  bool tag_name_compression = false;
+  std::optional<std::string> reset_value_to_field;
   std::vector<SegmentReq> segments;
 };
 

@@ -251,5 +251,46 @@ def evaluate_formula(engine, base_expressions: Dict[str, dict], formula: str,
             for t, _, v, tg in rows]
 
 
+def _filter_leaves(q: dict):
+    """The leaves of a filter JSON node (ASTUtils.handleFilter's shapes: `not`, leaf, binary node)."""
+    if q.get("not") is not None:
+        yield from _filter_leaves(q["not"])
+    elif q.get("k") is not None:
+        yield q
+    else:
+        for c in q.values():
+            if isinstance(c, dict):
+                yield from _filter_leaves(c)
+
+
+def is_tag_synthetic(base_expr: dict, tag_name: str) -> bool:
+    """BaseExpr.isTagSynthetic (BaseExpr.scala:146-157): the tag is an extracted or computed field of the filter."""
+    return any(f["k"] == tag_name and (f.get("extracted") or f.get("computed"))
+               for f in _filter_leaves(base_expr["filter"]))
+
+
+def evaluate_tag_query(engine, base_expr: dict, segment_requests: Sequence[dict], paths: Sequence[str],
+                       tag_data_type: Optional[dict] = None, limit: int = 1000, glob_size: int = 10) -> List[dict]:
+    """QueryEngineV2.evaluateTagQuery (QueryEngineV2.scala:419-491) for one SegmentGroup: with a tagDataType
+    ({"tagName", "dataType"}) whose tag is not synthetic the filter is ANDed with `exists` on the tag; the chart is
+    dropped; the pushdown carries isTagQuery and processor.tagNameCompressionEnabled.  Yields each row's tags map (the
+    GenericSSEPayload message), at most `limit` of them (QueryApi's take(limit)).  Without a tagDataType this is the
+    tag-name query: the engine returns every tag name once, on the first passing row that holds a value for it, rows of
+    a glob in file order and globs in request order (include/lakeside_gpu.h)."""
+    be = dict(base_expr)
+    if tag_data_type is not None and not is_tag_synthetic(be, tag_data_type["tagName"]):
+        be["filter"] = {"q1": be["filter"],
+                        "q2": {"k": tag_data_type["tagName"], "v": [], "op": "exists",
+                               "dataType": tag_data_type.get("dataType", "string"), "extracted": False, "computed": False},
+                        "op": "and"}
+    be.pop("chart", None)
+    req = {"baseExpr": be, "segmentRequests": list(segment_requests), "reverseSort": False, "isTagQuery": True,
+           "processor": {"tagNameCompressionEnabled": True}}
+    if tag_data_type is not None:
+        req["tagDataType"] = {"tagName": tag_data_type["tagName"], "dataType": tag_data_type.get("dataType", "string")}
+    res = engine.eval_pushdown(json.dumps(req), list(paths), glob_size, LK_MERGED)
+    return [{"message": dict(t)} for t in res.tags[:max(0, int(limit))]]
+
+
 __all__ = ["clause_string", "label", "group_by_key", "transformer", "eval_merged_rows", "evaluate_base_expr",
-           "formula_plan", "formula_label", "evaluate_formula"]
+           "formula_plan", "formula_label", "evaluate_formula", "is_tag_synthetic", "evaluate_tag_query"]
