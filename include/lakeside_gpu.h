@@ -66,6 +66,9 @@ enum {
  * -- instead of gathering values row by row, and from whose per-code element ranges name-filtered COUNT queries take
  * their counts without reading a value (AVG is the sum with those counts); false = no copy, for deployments that prefer
  * the cache capacity.
+ * cluster_samples (default true): a load also keeps, per tile of a segment whose timestamps are sorted, the 256
+ * timestamps that the search for a tile's bucket boundaries samples (2 KB per tile, counted in the cache weight, with
+ * or without cluster_values); false = no tables, the search reads the timestamp column.
  * Replaces DuckDbConnectionFactory (core/.../utils/DuckDbConnectionFactory.scala:76-114). */
 int lk_engine_create(const char* options_json, lk_engine** out);
 void lk_engine_destroy(lk_engine* e);

@@ -98,6 +98,13 @@ uint32_t lk_clu_sub_bytes(uint32_t nrows, uint32_t dict_n, uint32_t c, uint32_t 
  * nrows rows with boundary rows sb[0 .. nsb) (ascending; sb[k] = the first row of class k + 1; nsb <= 4), cls[j] = the
  * class of every row of sub-block j, or 0xffffffff when the sub-block's rows must be streamed.  Returns the sub-blocks. */
 uint32_t lk_clu_sub_sim(uint32_t nrows, const uint32_t* sb, uint32_t nsb, uint32_t* cls);
+/* A tile's timestamp sample table as clu_build lays it out (clu.hpp, clu_samp_row): given the tile's timestamps
+ * ts[0 .. nrows), table[s] = ts[(s * nrows) >> 8] for s = 0 .. 255, the rows scan_clu's boundary search samples (below
+ * 256 rows they repeat).  Returns 256, or -1 for nrows outside 1 .. 65,536. */
+int lk_clu_samples_sim(const int64_t* ts, uint32_t nrows, int64_t* table);
+/* The byte offset of tile `tile`'s table in a segment's area of sample tables (clu.hpp, clu_samp_tile_off); where
+ * non-NULL: samp_bytes = a table's size. */
+uint64_t lk_clu_samp_layout(uint32_t tile, uint32_t* samp_bytes);
 /* COUNT over a split tile needs no value (clu.hpp, clu_count_split, the arithmetic of scan_clu<AGG_COUNT>): the
  * per-class counts of one code of a tile of nrows rows (<= 65,536), given the rows within the tile of its n elements
  * (rows[0 .. n), strictly ascending: the code's crows) and the boundary rows sb[0 .. nsb) (ascending, nsb <= 4).  The

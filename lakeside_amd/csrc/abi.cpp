@@ -67,6 +67,7 @@ int lk_engine_create(const char* options_json, lk_engine** out) {
         lk::Json o = lk::Json::parse(options_json);
         if (const lk::Json* b = o.get("hbm_budget_bytes")) e->e->hbm_budget = size_t(b->as_i64());
         if (const lk::Json* c = o.get("cluster_values")) e->e->cluster_values = c->as_bool();
+        if (const lk::Json* c = o.get("cluster_samples")) e->e->cluster_samples = c->as_bool();
         if (const lk::Json* c = o.get("max_calls")) e->e->max_calls = size_t(std::max<int64_t>(1, c->as_i64()));
         if (const lk::Json* d = o.get("dict_compact_min_dead"))
           e->e->compact_min_dead = size_t(std::max<int64_t>(1, d->as_i64()));
@@ -136,9 +137,11 @@ const char* lk_engine_stats(lk_engine* e) {
     o += "\"segments\":" + std::to_string(E.cache.size()) + ",\"segment_bytes\":" + std::to_string(E.cache_bytes) +
          ",\"evictions\":" + std::to_string(E.evictions) + ",\"load_ms\":" + std::to_string(E.load_ms_total) +
          ",\"load_host_ms\":" + std::to_string(E.load_host_ms_total);
-    size_t clu = 0, sub = 0;   // the clustered value copies' and their sub-block areas' shares of segment_bytes
-    for (auto& kv : E.cache) clu += kv.second->clu_bytes, sub += kv.second->clu_sub_bytes;
-    o += ",\"clu_bytes\":" + std::to_string(clu) + ",\"clu_sub_bytes\":" + std::to_string(sub) + ",\"clu_alloc_failed\":" + std::to_string(E.clu_alloc_failed.load());
+    // the clustered value copies', their sub-block areas' and the timestamp sample tables' shares of segment_bytes
+    size_t clu = 0, sub = 0, samp = 0;
+    for (auto& kv : E.cache) clu += kv.second->clu_bytes, sub += kv.second->clu_sub_bytes, samp += kv.second->ts_samp_bytes;
+    o += ",\"clu_bytes\":" + std::to_string(clu) + ",\"clu_sub_bytes\":" + std::to_string(sub) +
+         ",\"clu_samp_bytes\":" + std::to_string(samp) + ",\"clu_alloc_failed\":" + std::to_string(E.clu_alloc_failed.load());
   }
   o += ",\"dict_compactions\":" + std::to_string(E.compactions) + ",\"dictionaries\":{";
   {

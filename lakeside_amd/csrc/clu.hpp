@@ -47,6 +47,17 @@ LK_BK_HD inline uint32_t clu_sub_bytes(uint32_t dict_n) {
   return (b + (CLU_BLOCK_ALIGN - 1u)) / CLU_BLOCK_ALIGN * CLU_BLOCK_ALIGN;
 }
 
+// A tile's timestamp sample table: CLU_SAMP_N raw 8-B timestamps, entry s the one of row clu_samp_row(s, nrows) -- the
+// rows the first round of scan_clu's boundary search samples, 2 KB apart in a full tile's timestamp stream and here 16
+// consecutive 128-B lines a wave loads in four coalesced rounds beside its filter chain.  A property of the segment's
+// timestamp column (every tile sorted, PLAIN64), not of the copy: the tables form an area of their own, tile t's at
+// clu_samp_tile_off(t), allocated in front of the sub-block area where the segment has one, so scan_clu finds it
+// QSeg::clu_samp_back bytes below QSeg::clu_sub (0: the segment has no tables and the search samples the column).
+constexpr uint32_t CLU_SAMP_N = 256;
+constexpr uint32_t CLU_SAMP_BYTES = CLU_SAMP_N * 8u;   // a multiple of CLU_BLOCK_ALIGN
+LK_BK_HD inline uint32_t clu_samp_row(uint32_t s, uint32_t nrows) { return uint32_t((uint64_t(s) * nrows) >> 8); }   // s = 256: nrows
+LK_BK_HD inline uint64_t clu_samp_tile_off(uint32_t t) { return uint64_t(t) * CLU_SAMP_BYTES; }
+
 // Sub-block j of a split tile of nrows rows, rows [lo, hi) = [CLU_SUB_ROWS * j, min(CLU_SUB_ROWS * (j + 1), nrows)),
 // against the tile's boundary rows sb[0 .. nsb) (ascending; sb[k] is the first row of class k + 1): the sub-block is
 // whole when no boundary lies strictly inside (lo, hi) -- one exactly on its first row leaves it whole -- and then

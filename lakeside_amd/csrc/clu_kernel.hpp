@@ -24,13 +24,21 @@
 // then the one shuffle tree and the one merge per (tile, code, class).  LK_NO_CLU_SUB=1 (SPLIT_OK_NO_CLU_SUB), or a
 // segment without the area, streams the ranges whole: bit for bit the same MIN, MAX and integral sums, real sums within
 // the suite's bar (the double-double partials combine in another order).
+// The search's first round does not wait behind the filter chain: the 256 sampled timestamps lie in the tile's sample
+// table in front of the sub-block area (clu.hpp; copied at load by clu_samp_build), 16 consecutive lines that the
+// wave loads in four coalesced rounds as soon as CluTile has arrived and classes behind the truth word's ballot; the
+// first passing code's csub / sagg entries are issued before the search as well, so they share its round trips.  The
+// gap round reads the timestamp column itself.  LK_NO_CLU_SAMP=1 (SPLIT_OK_NO_CLU_SAMP), or a segment without the table
+// (cluster_samples off), samples the column as before -- 256 lines 2 KB apart in a full tile: the same timestamps, so
+// the same boundaries and rows bit for bit.  QSeg's fields of the area are read with its other fields at the top.
 // No run staging, no chunk table, no row list, no LDS.  global_merge honours the LEAN_* flags, the -0.0 empty marker,
 // exact_sum and FLAG_MIN_NAN.  LK_NO_CLU_AGG=1 (SPLIT_OK_NO_CLU_AGG) streams pinned tiles too, with clu_reduce_pinned
 // (one merge per (tile, code)): the same rows bit for bit, the A/B and the tests' proof of which path ran.
 //
 // Shape: one wave per tile, four tiles per 256-thread workgroup, no barrier.  A pinned tile is a chain of dependent
 // loads (QSeg -> TileDesc / CluTile / TileCol -> remap, cpref, cagg -> strtab -> truth word) and a few atomics; at a
-// 1 m step three of C2's four tiles are pinned.  A split tile of C2 has about 4,096 passing values (32 KB): a wave
+// 1 m step three of C2's four tiles are pinned.  A split tile adds the boundary search (the sample table beside the
+// chain above, then the gap rows) and its codes' sub-block entries and straddlers.  A split tile of C2 has about 4,096 passing values (32 KB): a wave
 // holds 8 loads per lane of values and of rows in flight; the stream is latency-bound, so what counts is bytes in flight
 // per CU, and a wave per tile needs no cross-wave reduction.  Measured: C2's scan 0.159 -> 0.101 ms in the
 // kernel trace with the aggregates (1.114 ms before the copy), plan bytes 0.585 -> 0.165 GB.  A workgroup per tile and
@@ -61,6 +69,10 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
     if (lane == 0) atomicOr(P.flags, FLAG_CELL_RANGE);
     return;
   }
+  // QSeg's fields of the sub-block area, read here with its other fields: a read behind the tests that need it is one
+  // more dependent round trip of the tile's chain
+  const uint8_t* const sub_base = uni_ptr(Sp->clu_sub);
+  const uint32_t sub_stride = uni(Sp->clu_sub_stride), samp_back = uni(Sp->clu_samp_back);
   const CluTile d = Sp->clu[t];
   const TileCol* tc0 = Sp->cols[0].tcols + t;
   const TileCol* tc2 = Sp->cols[2].tcols + t;
@@ -87,6 +99,22 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
       if (lane < clu_dict_n(d.dict_n)) ag = reinterpret_cast<const CluAgg*>(blk + CLU_AGG_OFF)[lane];
       if (AGG == AGG_MIN) nanw = *reinterpret_cast<const unsigned long long*>(blk + CLU_NAN_OFF);
     }
+  }
+  // A split tile's 256 timestamp samples (the first round of the boundary search below) from the tile's sample table
+  // (clu.hpp; QSeg::clu_samp_back bytes below the sub-block area): lane l holds samples l, l + 64, l + 128, l + 192 -- four coalesced loads, 16 lines.  They
+  // depend on CluTile alone and are issued here, beside the filter chain, and consumed behind the truth word's ballot.
+  // LK_NO_CLU_SAMP=1 (SPLIT_OK_NO_CLU_SAMP), or a segment without the table: the search samples the timestamp column.
+  const bool use_samp = cc.kind == CLU_SPLIT && sub_base != nullptr && !(P.split_ok & SPLIT_OK_NO_CLU_SAMP) &&
+                        d.nrows <= tdp->nrows && clu_samp_tile_off(t) + CLU_SAMP_BYTES <= samp_back;   // uniform
+  v2u tsamp[CLU_SAMP_N / 64u];
+#pragma unroll
+  for (uint32_t j = 0; j < CLU_SAMP_N / 64u; j++) tsamp[j] = v2u{0u, 0u};
+  if (use_samp) {
+    const __amdgpu_buffer_rsrc_t rsm =
+        make_rsrc(sub_base - samp_back + clu_samp_tile_off(t), CLU_SAMP_BYTES);
+#pragma unroll
+    for (uint32_t j = 0; j < CLU_SAMP_N / 64u; j++)
+      tsamp[j] = __builtin_amdgcn_raw_buffer_load_b64(rsm, (lane + 64u * j) * 8u, 0, 0);
   }
 
   // passing codes: one ballot over the chunk dictionary (Kleene: the leaves' T/F bits of the code), as scan_lean
@@ -149,9 +177,51 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
   const __amdgpu_buffer_rsrc_t rv = make_rsrc(blk + clu_vals_off(d.dict_n), nrows * 8u);
   const uint16_t* crows = reinterpret_cast<const uint16_t*>(blk + clu_rows_off(nrows, d.dict_n));
 
-  // split tiles: boundary rows (scan_lean's search, per wave: four samples / gap rows per lane)
   const bool split = cc.kind == CLU_SPLIT;
   const uint32_t nsb = cc.nsb;
+  // A split tile's sub-block area (clu.hpp): the whole sub-blocks of a passing code hand on their stored aggregates
+  // (COUNT: their element counts), only the straddling ones are streamed.  LK_NO_CLU_SUB=1, or a segment without the
+  // area: the range streams whole.
+  const bool use_sub = split && sub_base != nullptr && !(P.split_ok & SPLIT_OK_NO_CLU_SUB) && d.nrows <= tdp->nrows &&
+                       clu_sub_bytes(d.dict_n) <= sub_stride && dict_n <= clu_dict_n(d.dict_n);   // uniform
+  const __amdgpu_buffer_rsrc_t rsub =
+      make_rsrc(use_sub ? sub_base + uint64_t(t) * sub_stride : nullptr, use_sub ? clu_sub_bytes(d.dict_n) : 0u);
+  const uint32_t nsub = clu_nsub(nrows);
+  // lane j: code c's elements [a, b) of sub-block j (csub) and, but for COUNT, their aggregate (sagg: SUM hi, lo; MIN /
+  // MAX the extreme; MIN also the code's NaN bits, a uint16 inside an aligned word), one round of loads through the
+  // area's buffer resource (uniform base and entry offset, the lane's offset in one register).  They depend on c alone:
+  // the first passing code's are issued before the boundary search below, whose round trips they then share.
+  struct SubEnt {
+    uint32_t a, b;
+    v2u g0, g1;
+    uint32_t snan;
+  };
+  auto load_sub = [&](uint32_t c) __attribute__((always_inline)) -> SubEnt {
+    SubEnt en{0u, 0u, v2u{0u, 0u}, v2u{0u, 0u}, 0u};
+    const bool sl = lane < nsub;
+    const uint32_t co = clu_sub_csub_off(d.dict_n) + c * (CLU_SUB_MAX + 1u) * 4u;
+    en.a = __builtin_amdgcn_raw_buffer_load_b32(rsub, sl ? lane * 4u : OOB, int(co), 0);
+    en.b = __builtin_amdgcn_raw_buffer_load_b32(rsub, sl ? lane * 4u + 4u : OOB, int(co), 0);
+    if (AGG != AGG_COUNT) {
+      const uint32_t go = sl ? lane * uint32_t(sizeof(CluAgg)) : OOB;
+      if (AGG == AGG_SUM) {
+        const v4u g = __builtin_amdgcn_raw_buffer_load_b128(rsub, go, int(clu_sub_sagg_off(c, 0u)), 0);
+        en.g0 = v2u{g.x, g.y};
+        en.g1 = v2u{g.z, g.w};
+      } else {
+        en.g0 = __builtin_amdgcn_raw_buffer_load_b64(rsub, go, int(clu_sub_sagg_off(c, 0u) + (AGG == AGG_MIN ? 16u : 24u)), 0);
+      }
+      if (AGG == AGG_MIN) {
+        const uint32_t no = clu_sub_nan_off(d.dict_n) + c * 2u;
+        en.snan = (__builtin_amdgcn_raw_buffer_load_b32(rsub, 0u, int(no & ~3u), 0) >> ((no & 2u) * 8u)) & 0xffffu;
+      }
+    }
+    return en;
+  };
+  SubEnt pre{0u, 0u, v2u{0u, 0u}, v2u{0u, 0u}, 0u};
+  if (use_sub) pre = load_sub(uint32_t(__builtin_ctzll(emask)));   // uniform (emask != 0 here)
+
+  // split tiles: boundary rows (scan_lean's search, per wave: four samples / gap rows per lane)
   uint32_t sb[CLU_SPLIT_MAX];
 #pragma unroll
   for (uint32_t k = 0; k < CLU_SPLIT_MAX; k++) sb[k] = 0xffffffffu;
@@ -165,7 +235,7 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
       return uint32_t(bucket_mono(ts, P.step, P.bucket_base, false) - cc.b0) + 1u;
     };
     auto sample = [&](uint32_t s) __attribute__((always_inline)) -> uint32_t {   // row of sample s (s = 256: nrows)
-      return uint32_t((uint64_t(s) * nrows) >> 8);
+      return clu_samp_row(s, nrows);
     };
     auto ts_at = [&](uint32_t r, bool live) __attribute__((always_inline)) -> int64_t {
       const v2u x = __builtin_amdgcn_raw_buffer_load_b64(rst, live ? (vbt + r) * 8u : OOB, 0, 0);
@@ -174,9 +244,29 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
     uint32_t scnt[CLU_SPLIT_MAX];   // per class boundary k: the samples below class k + 1 (uniform)
 #pragma unroll
     for (uint32_t k = 0; k < CLU_SPLIT_MAX; k++) scnt[k] = 0u;
+    // the samples: the table's entries loaded above, or the column's rows they were copied from (the same timestamps)
+    int64_t tss[CLU_SAMP_N / 64u];
+    uint32_t samp_lines = CLU_SAMP_BYTES / 128u;   // plan bytes: the 128-B lines the samples touch
+    if (use_samp) {   // uniform
 #pragma unroll
-    for (uint32_t j = 0; j < 4; j++) {
-      const uint32_t c = cls_of(ts_at(sample(lane + 64u * j), true));
+      for (uint32_t j = 0; j < CLU_SAMP_N / 64u; j++) tss[j] = int64_t(((uint64_t)tsamp[j].y << 32) | tsamp[j].x);
+    } else {
+#pragma unroll
+      for (uint32_t j = 0; j < CLU_SAMP_N / 64u; j++) tss[j] = ts_at(sample(lane + 64u * j), true);
+      if (count_plan) {   // a line per sample whose line is not the sample's before (rows ascend)
+        const uint32_t a0 = uint32_t(reinterpret_cast<uint64_t>(Sp->base + tc0->vals));
+        samp_lines = 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < CLU_SAMP_N / 64u; j++) {
+          const uint32_t s = lane + 64u * j;
+          const uint32_t ln = (a0 + (vbt + sample(s)) * 8u) >> 7, lp = (a0 + (vbt + sample(s ? s - 1u : 0u)) * 8u) >> 7;
+          samp_lines += uint32_t(__popcll(__ballot(s == 0u || ln != lp)));
+        }
+      }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < CLU_SAMP_N / 64u; j++) {
+      const uint32_t c = cls_of(tss[j]);
 #pragma unroll
       for (uint32_t k = 0; k < CLU_SPLIT_MAX; k++)
         if (k < nsb) scnt[k] += uint32_t(__popcll(__ballot(c < k + 1u)));
@@ -204,7 +294,7 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
       }
       sb[k] = b;
     }
-    if (count_plan && lane == 0) pbytes += sizeof(TileCol) + 128u * (256u / 16u + nsb * 2u);   // sample and gap lines (approx.)
+    if (count_plan && lane == 0) pbytes += sizeof(TileCol) + 128u * (samp_lines + nsb * 2u);   // sample lines, gap lines (approx.)
   }
   auto split_class = [&](uint32_t r) __attribute__((always_inline)) -> uint32_t {
     uint32_t c = 0;
@@ -220,17 +310,16 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
   // streamed; without it (LK_NO_CLU_SUB=1, or no area) the code's whole crows range is.  crows: one 2-B load per lane
   // per step, eight steps in flight, as the SUM path loads them.  Counts are exact uint32 (a tile has <= 65,536 rows).
   if constexpr (AGG == AGG_COUNT) {
-    const bool use_sub = Sp->clu_sub != nullptr && !(P.split_ok & SPLIT_OK_NO_CLU_SUB) && d.nrows <= tdp->nrows &&
-                         clu_sub_bytes(d.dict_n) <= Sp->clu_sub_stride && dict_n <= clu_dict_n(d.dict_n);   // uniform
-    const __amdgpu_buffer_rsrc_t rsub =
-        make_rsrc(use_sub ? Sp->clu_sub + uint64_t(t) * Sp->clu_sub_stride : nullptr, use_sub ? clu_sub_bytes(d.dict_n) : 0u);
-    const uint32_t nsub = clu_nsub(nrows);
     uint32_t subc = CLU_SUB_STRADDLE;
     if (use_sub && lane < nsub) subc = clu_sub_class(lane, nrows, sb, nsb);
     constexpr uint32_t NK = CLU_SPLIT_MAX - 1u;   // the in-window classes 1 .. nsb - 1
+    bool first = true;
     while (emask) {
       const uint32_t c = uint32_t(__builtin_ctzll(emask));
       emask &= emask - 1ull;
+      SubEnt en = pre;   // the first passing code's entries were loaded before the search
+      if (use_sub && !first) en = load_sub(c);   // uniform
+      first = false;
       const uint32_t s = uni(__shfl(cs, int(c), 64)), e = uni(__shfl(ce, int(c), 64));
       if (s >= e) continue;   // the name is absent from the tile
       const uint32_t dim = (uni(__shfl(lut, int(c), 64)) & DIM_MASK) * stride;
@@ -263,8 +352,7 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
       } else {
         const bool sl = lane < nsub;
         const uint32_t co = clu_sub_csub_off(d.dict_n) + c * (CLU_SUB_MAX + 1u) * 4u;
-        uint32_t a = __builtin_amdgcn_raw_buffer_load_b32(rsub, sl ? lane * 4u : OOB, int(co), 0);
-        uint32_t b = __builtin_amdgcn_raw_buffer_load_b32(rsub, sl ? lane * 4u + 4u : OOB, int(co), 0);
+        uint32_t a = en.a, b = en.b;
         if (!sl) a = b = e;
         clu_sub_clamp(a, b, s, e);
         if (subc != CLU_SUB_STRADDLE && subc >= 1u && subc < nsb && a < b) {
@@ -321,13 +409,6 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
     return;
   }
 
-  // A split tile's sub-block area (clu.hpp): the whole sub-blocks of a passing code hand on their stored aggregates,
-  // only the straddling ones are streamed.  LK_NO_CLU_SUB=1, or a segment without the area: the range streams whole.
-  const bool use_sub = split && Sp->clu_sub != nullptr && !(P.split_ok & SPLIT_OK_NO_CLU_SUB) && d.nrows <= tdp->nrows &&
-                       clu_sub_bytes(d.dict_n) <= Sp->clu_sub_stride && dict_n <= clu_dict_n(d.dict_n);   // uniform
-  const __amdgpu_buffer_rsrc_t rsub =
-      make_rsrc(use_sub ? Sp->clu_sub + uint64_t(t) * Sp->clu_sub_stride : nullptr, use_sub ? clu_sub_bytes(d.dict_n) : 0u);
-  const uint32_t nsub = clu_nsub(nrows);
   // lane j: sub-block j's class, CLU_SUB_STRADDLE when its rows' classes differ (the same for every code)
   uint32_t subc = CLU_SUB_STRADDLE;
   if (use_sub && lane < nsub) subc = clu_sub_class(lane, nrows, sb, nsb);
@@ -428,9 +509,13 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
     finish(dim);
   }
   // Split tiles with the sub-block area.
+  bool first = true;
   while (emask) {
     const uint32_t c = uint32_t(__builtin_ctzll(emask));
     emask &= emask - 1ull;
+    SubEnt en = pre;   // the first passing code's entries were loaded before the search
+    if (!first) en = load_sub(c);   // uniform
+    first = false;
     const uint32_t s = uni(__shfl(cs, int(c), 64)), e = uni(__shfl(ce, int(c), 64));
     if (s >= e) continue;   // the name is absent from the tile
     const uint32_t dim = (uni(__shfl(lut, int(c), 64)) & DIM_MASK) * stride;
@@ -440,26 +525,11 @@ __global__ __launch_bounds__(BLOCK) void scan_clu(QParams P) {
       ext[k] = AGG == AGG_MIN ? ~0ull : 0ull;
       cnt[k] = 0u;
     }
-    // lane j: the code's elements [a, b) of sub-block j and their aggregate, one round of loads through the
-    // area's buffer resource (uniform base and entry offset, the lane's offset in one register)
+    // lane j: the code's elements [a, b) of sub-block j and their aggregate (load_sub)
     const bool sl = lane < nsub;
-    const uint32_t co = clu_sub_csub_off(d.dict_n) + c * (CLU_SUB_MAX + 1u) * 4u;
-    uint32_t a = __builtin_amdgcn_raw_buffer_load_b32(rsub, sl ? lane * 4u : OOB, int(co), 0);
-    uint32_t b = __builtin_amdgcn_raw_buffer_load_b32(rsub, sl ? lane * 4u + 4u : OOB, int(co), 0);
-    const uint32_t go = sl ? lane * uint32_t(sizeof(CluAgg)) : OOB;
-    v2u g0, g1 = v2u{0u, 0u};   // SUM: hi, lo; MIN / MAX: the extreme
-    if (AGG == AGG_SUM) {
-      const v4u g = __builtin_amdgcn_raw_buffer_load_b128(rsub, go, int(clu_sub_sagg_off(c, 0u)), 0);
-      g0 = v2u{g.x, g.y};
-      g1 = v2u{g.z, g.w};
-    } else {
-      g0 = __builtin_amdgcn_raw_buffer_load_b64(rsub, go, int(clu_sub_sagg_off(c, 0u) + (AGG == AGG_MIN ? 16u : 24u)), 0);
-    }
-    uint32_t snan = 0u;   // MIN: the code's NaN bits (a uint16 inside an aligned word)
-    if (AGG == AGG_MIN) {
-      const uint32_t no = clu_sub_nan_off(d.dict_n) + c * 2u;
-      snan = (__builtin_amdgcn_raw_buffer_load_b32(rsub, 0u, int(no & ~3u), 0) >> ((no & 2u) * 8u)) & 0xffffu;
-    }
+    uint32_t a = en.a, b = en.b;
+    const v2u g0 = en.g0, g1 = en.g1;   // SUM: hi, lo; MIN / MAX: the extreme
+    const uint32_t snan = en.snan;      // MIN: the code's NaN bits
     if (!sl) a = b = e;
     b = b < e ? b : e;   // clamped to the code's range, as cpref is clamped to the tile's rows
     b = b > s ? b : s;

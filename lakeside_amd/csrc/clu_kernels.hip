@@ -180,7 +180,27 @@ __global__ __launch_bounds__(BLOCK) void clu_build(CluBuild B) {
   if (has_sub && tid < dict_n) reinterpret_cast<uint16_t*>(sblk + clu_sub_nan_off(dict_n))[tid] = uint16_t(snan[tid]);
 }
 
+// clu_samp_build: the timestamp sample tables of a segment whose every tile has sorted PLAIN64 timestamps (clu.hpp):
+// one workgroup per tile, thread s copies the raw timestamp of row clu_samp_row(s, nrows) to entry s of the tile's
+// table.  The read goes through a buffer resource over the tile's stream, the store stays inside the tile's table.
+__global__ __launch_bounds__(CLU_SAMP_N) void clu_samp_build(SampBuild B) {
+  const uint32_t t = blockIdx.x, s = threadIdx.x;
+  if (t >= B.ntiles || s >= CLU_SAMP_N) return;
+  const uint32_t n = B.tiles[t].nrows;
+  const uint32_t nrows = n < TILE_ROWS ? n : TILE_ROWS;
+  const TileCol* tt = B.ts_tc + t;
+  const __amdgpu_buffer_rsrc_t rts = make_rsrc(B.base + tt->vals, tt->vals_len);
+  const v2u x = __builtin_amdgcn_raw_buffer_load_b64(rts, (tt->vbase + clu_samp_row(s, nrows)) * 8u, 0, 0);
+  reinterpret_cast<unsigned long long*>(B.samp + clu_samp_tile_off(t))[s] = ((unsigned long long)x.y << 32) | x.x;
+}
+
 }  // namespace
+
+hipError_t launch_clu_samp_build(const SampBuild& B, hipStream_t st) {
+  if (B.ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(clu_samp_build, dim3(B.ntiles), dim3(CLU_SAMP_N), 0, st, B);
+  return hipGetLastError();
+}
 
 hipError_t launch_clu_build(const CluBuild& B, hipStream_t st) {
   if (B.ntiles == 0) return hipSuccess;

@@ -42,6 +42,18 @@ extern "C" uint32_t lk_clu_sub_sim(uint32_t nrows, const uint32_t* sb, uint32_t 
   return n;
 }
 
+extern "C" int lk_clu_samples_sim(const int64_t* ts, uint32_t nrows, int64_t* table) {
+  using namespace lk;
+  if (nrows == 0 || nrows > TILE_ROWS) return -1;
+  for (uint32_t s = 0; s < CLU_SAMP_N; s++) table[s] = ts[clu_samp_row(s, nrows)];
+  return int(CLU_SAMP_N);
+}
+
+extern "C" uint64_t lk_clu_samp_layout(uint32_t tile, uint32_t* samp_bytes) {
+  if (samp_bytes) *samp_bytes = lk::CLU_SAMP_BYTES;
+  return lk::clu_samp_tile_off(tile);
+}
+
 extern "C" int lk_clu_count_sim(uint32_t nrows, const uint16_t* rows, uint32_t n, const uint32_t* sb, uint32_t nsb,
                                 int use_sub, uint32_t* cnt) {
   using namespace lk;

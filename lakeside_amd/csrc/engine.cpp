@@ -453,7 +453,8 @@ Segment::~Segment() {
   if (d_data) (void)hipFree(d_data);
   if (d_meta) (void)hipFree(d_meta);
   if (d_clu) (void)hipFree(d_clu);
-  if (d_clu_sub) (void)hipFree(d_clu_sub);
+  if (d_clu_sub && !clu_sub_shared) (void)hipFree(d_clu_sub);   // (shared: part of d_ts_samp's allocation)
+  if (d_ts_samp) (void)hipFree(d_ts_samp);
 }
 
 int Engine::load_thread_count() const {
@@ -534,7 +535,9 @@ std::shared_ptr<Segment> Engine::build_segment(const std::string& key, const uin
   }
   HIP_CHECK(hipMemcpyAsync(S->d_meta, blob.data(), off, hipMemcpyHostToDevice, load_stream));
   HIP_CHECK(hipStreamSynchronize(load_stream));   // `blob` is freed on return
-  if (cluster_values) build_cluster(*S);
+  const int ts_samp_col = cluster_samples ? samples_eligible(*S) : -1;
+  if (cluster_values) build_cluster(*S, ts_samp_col >= 0);
+  if (ts_samp_col >= 0) build_samples(*S, ts_samp_col);
   // the segment now references its chunk dictionaries' ids (released by ~Segment)
   S->engine = this;
   for (auto& c : S->cols)
@@ -558,7 +561,44 @@ std::shared_ptr<Segment> Engine::build_segment(const std::string& key, const uin
 // from the streams just uploaded (cagg: every code's values reduced once, for scan_clu's pinned tiles).  The host loader, the staged bytes and the host link traffic are what they were; the descriptors are the only upload.
 // An allocation that fails leaves the segment without a copy (it serves every query on the other kernels) and is
 // counted (clu_alloc_failed).
-void Engine::build_cluster(Segment& S) {
+// The timestamp sample tables (clu.hpp): for a segment whose every tile has sorted, NULL-free PLAIN64 timestamps -- the
+// tiles whose bucket boundaries a kernel finds by searching the timestamps.  2 KB per tile, counted in the cache weight.
+int Engine::samples_eligible(const Segment& S) const {
+  const int ct = S.col_index(kTimestamp);
+  const size_t nt = S.tiles.size();
+  if (ct < 0 || nt == 0 || nt * size_t(CLU_SAMP_BYTES) >= (size_t(1) << 32)) return -1;
+  const HostCol& T = S.cols[size_t(ct)];
+  if (T.is_string || T.tcols.size() != nt) return -1;
+  for (size_t t = 0; t < nt; t++) {
+    const TileCol& c = T.tcols[t];
+    const TileDesc& td = S.tiles[t];
+    if (c.kind != PAGE_PLAIN64 || c.has_nulls || !(td.pad & TILE_TS_SORTED) || td.nrows < 1 || td.nrows > TILE_ROWS) return -1;
+  }
+  return ct;
+}
+
+void Engine::build_samples(Segment& S, int ts_col) {
+  const size_t nt = S.tiles.size();
+  if (!S.d_ts_samp) {   // no sub-block area to share an allocation with
+    if (hipMalloc(&S.d_ts_samp, nt * size_t(CLU_SAMP_BYTES)) != hipSuccess) {
+      (void)hipGetLastError();
+      S.d_ts_samp = nullptr;   // not an error: the search samples the column
+      return;
+    }
+    S.ts_samp_bytes = nt * size_t(CLU_SAMP_BYTES);
+  }
+  SampBuild B{};
+  B.base = S.d_data;
+  B.tiles = S.d_tiles;
+  B.ts_tc = S.cols[size_t(ts_col)].d_tcols;
+  B.samp = S.d_ts_samp;
+  B.ntiles = uint32_t(nt);
+  HIP_CHECK(launch_clu_samp_build(B, load_stream));
+  HIP_CHECK(hipStreamSynchronize(load_stream));
+  S.ts_samp_col = ts_col;
+}
+
+void Engine::build_cluster(Segment& S, bool with_samples) {
   const int cn = S.col_index(kName), cv = S.col_index(kValue);
   const size_t nt = S.tiles.size();
   if (cn < 0 || cv < 0 || nt == 0) return;
@@ -598,13 +638,23 @@ void Engine::build_cluster(Segment& S) {
   S.clu_bytes = off;
   // The sub-block area: a fixed stride per tile, the segment's largest dict_n.  Without it (the allocation failed) the
   // segment keeps its copy and its split tiles stream whole: not an error.
+  // With the timestamp sample tables (build_samples fills them) one allocation holds both, the tables first: scan_clu
+  // finds them QSeg::clu_samp_back bytes below the area.
   S.clu_sub_stride = clu_sub_bytes(max_dict_n);
-  if (hipMalloc(&S.d_clu_sub, nt * size_t(S.clu_sub_stride)) != hipSuccess) {
+  const size_t samp_part = with_samples ? nt * size_t(CLU_SAMP_BYTES) : 0;   // a multiple of CLU_BLOCK_ALIGN
+  uint8_t* area = nullptr;
+  if (hipMalloc(&area, samp_part + nt * size_t(S.clu_sub_stride)) != hipSuccess) {
     (void)hipGetLastError();
     S.d_clu_sub = nullptr;
     S.clu_sub_stride = 0;
   } else {
+    S.d_clu_sub = area + samp_part;
     S.clu_sub_bytes = nt * size_t(S.clu_sub_stride);
+    if (samp_part) {
+      S.d_ts_samp = area;
+      S.ts_samp_bytes = samp_part;
+      S.clu_sub_shared = true;
+    }
   }
   S.d_clu_desc = reinterpret_cast<const CluTile*>(S.d_clu);
   HIP_CHECK(hipMemcpyAsync(S.d_clu, desc.data(), nt * sizeof(CluTile), hipMemcpyHostToDevice, load_stream));

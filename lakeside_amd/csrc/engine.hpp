@@ -46,11 +46,20 @@ struct Segment : SegmentData {
   uint8_t* d_clu_sub = nullptr;
   size_t clu_sub_bytes = 0;
   uint32_t clu_sub_stride = 0;
+  // The timestamp sample tables (clu.hpp: 2 KB per tile, the timestamps of column ts_samp_col), for segments whose
+  // every tile has sorted PLAIN64 timestamps -- a property of the timestamp column, whether or not the segment has a
+  // copy; null when the engine option is off, the segment does not qualify or the allocation failed.  Where the segment
+  // has a sub-block area the two share one allocation, tables first (clu_sub_shared: d_clu_sub points into it), so
+  // scan_clu reaches the tables from QSeg::clu_sub without another pointer.
+  uint8_t* d_ts_samp = nullptr;
+  size_t ts_samp_bytes = 0;
+  int ts_samp_col = -1;
+  bool clu_sub_shared = false;
   int clu_name_col = -1, clu_val_col = -1;
   uint32_t clu_tiles = 0;
   bool clu_all_sorted = false;
   int64_t clu_widest = -1;
-  size_t hbm_bytes() const { return data_bytes + meta_bytes + clu_bytes + clu_sub_bytes; }   // the segment's cache weight
+  size_t hbm_bytes() const { return data_bytes + meta_bytes + clu_bytes + clu_sub_bytes + ts_samp_bytes; }   // the segment's cache weight
   bool from_put = false;                         // registered by lk_segment_put (its key is not a file path)
   std::atomic<uint64_t> last_use{0};             // LRU clock value of the last lookup (cache eviction)
   struct Engine* engine = nullptr;               // whose dictionaries its remaps reference (refs released at ~Segment)
@@ -179,6 +188,9 @@ struct Engine {
   // lk_engine_create {"cluster_values": false}: segments load without the name-clustered value copy (10 B per row of
   // eligible tiles), for deployments that prefer the cache capacity to scan_clu
   bool cluster_values = true;
+  // lk_engine_create {"cluster_samples": false}: segments load without the timestamp sample tables (2 KB per tile);
+  // scan_clu's boundary search then samples the timestamp column
+  bool cluster_samples = true;
   std::atomic<size_t> clu_alloc_failed{0};       // loads whose copy allocation failed (the segment serves the old path)
   std::atomic<uint64_t> use_clock{0};
   size_t evictions = 0;
@@ -250,7 +262,11 @@ struct Engine {
   ~Engine();
   GlobalDict& dict(const std::string& col);
   std::shared_ptr<Segment> build_segment(const std::string& key, const uint8_t* data, size_t size);
-  void build_cluster(Segment& S);                // caller holds dev_mu; S's host tile / column tables still present
+  // caller holds dev_mu; S's host tile / column tables still present.  with_samples: the segment qualifies for the
+  // timestamp sample tables (samples_eligible), which then share the sub-block area's allocation
+  void build_cluster(Segment& S, bool with_samples);
+  int samples_eligible(const Segment& S) const;   // the timestamp column's index, or -1
+  void build_samples(Segment& S, int ts_col);     // allocates the tables where build_cluster has not, and fills them
   int put_segment(const std::string& key, const uint8_t* data, size_t size, bool from_put = true);
   std::shared_ptr<Segment> get_segment(const std::string& key, bool load_on_miss);
   std::unique_ptr<CallCtx> acquire_ctx();

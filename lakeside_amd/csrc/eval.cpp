@@ -355,6 +355,9 @@ void setup_scan(const EvalCall& C, const Plan& pl, DevState& dv) {
   if (dv.P.split_ok && getenv("LK_NO_CLU_AGG")) dv.P.split_ok |= SPLIT_OK_NO_CLU_AGG;
   // LK_NO_CLU_SUB=1 (read per call, independent of the above): scan_clu streams its split tiles' ranges whole
   if (dv.P.split_ok && getenv("LK_NO_CLU_SUB")) dv.P.split_ok |= SPLIT_OK_NO_CLU_SUB;
+  // LK_NO_CLU_SAMP=1 (read per call, independent of the above): scan_clu's boundary search samples the timestamp column
+  // instead of loading the tile's sample table
+  if (dv.P.split_ok && getenv("LK_NO_CLU_SAMP")) dv.P.split_ok |= SPLIT_OK_NO_CLU_SAMP;
   // scan_lean (and, in COUNT / p<NN> / ces calls, scan_tiles) tests the value leaves of every row its string conjuncts pass
   if (pl.fp.vleaf && !pl.sg.qsegs.empty()) {
     dv.P.nvl = uint32_t(pl.fp.nleaves.size());

@@ -891,6 +891,9 @@ void plan_segments(const EvalCall& C, const QueryShape& qs, const FilterPlan& fp
         q.clu_base = S.d_clu;
         q.clu_sub = S.d_clu_sub;
         q.clu_sub_stride = S.clu_sub_stride;
+        // the sample tables (this timestamp column's) lie in front of the area, in its allocation
+        if (S.d_clu_sub && S.clu_sub_shared && S.d_ts_samp && S.ts_samp_col == S.col_index(kTimestamp))
+          q.clu_samp_back = uint32_t(S.d_clu_sub - S.d_ts_samp);
       }
       q.tile_begin = sg.total_tiles;
       sg.seg_begin.push_back(sg.total_tiles);
@@ -940,7 +943,7 @@ void plan_table_mode(const QueryShape& qs, const SegPlan& sg, CellSpace& cs) {
 
 void plan_cluster(const CellSpace& cs, SegPlan& sg) {
   if (cs.hash_mode)   // scan_clu merges into dense tables only
-    for (auto& q : sg.qsegs) q.clu = nullptr, q.clu_base = nullptr, q.clu_sub = nullptr, q.clu_sub_stride = 0;
+    for (auto& q : sg.qsegs) q.clu = nullptr, q.clu_base = nullptr, q.clu_sub = nullptr, q.clu_sub_stride = 0, q.clu_samp_back = 0;
   sg.n_clu = 0;
   if (std::none_of(sg.qsegs.begin(), sg.qsegs.end(), [](const QSeg& q) { return q.clu != nullptr; })) return;
   // (stable: each kind keeps its order; QSeg::tile_begin is a statistic, no kernel indexes by it)

@@ -296,6 +296,15 @@ struct CluBuild {
   uint32_t ntiles;
 };
 hipError_t launch_clu_build(const CluBuild& B, hipStream_t stream);
+// clu_samp_build (clu_kernels.hip): the timestamp sample tables (clu.hpp) of every tile of one segment
+struct SampBuild {
+  const uint8_t* base;             // segment streams
+  const TileDesc* tiles;           // per tile (nrows)
+  const TileCol* ts_tc;            // per tile: the timestamp column (PLAIN64, no NULL)
+  uint8_t* samp;                   // the tables' area: tile t's at clu_samp_tile_off(t), ntiles tables
+  uint32_t ntiles;
+};
+hipError_t launch_clu_samp_build(const SampBuild& B, hipStream_t stream);
 // lean tables: restore the rows / cnt fields the scan did not accumulate (LEAN_* in layout.hpp)
 hipError_t launch_remap_ids(uint32_t* p, unsigned long long n, const uint32_t* map, hipStream_t stream);
 hipError_t launch_fixup_table(const QParams& P, unsigned long long nc, int agg, hipStream_t stream);

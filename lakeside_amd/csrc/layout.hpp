@@ -150,7 +150,9 @@ struct QSeg {
   // has none, its split tiles stream their ranges whole
   const uint8_t* clu_sub;
   uint32_t clu_sub_stride;
-  uint32_t pad1;
+  // the segment's timestamp sample tables (clu.hpp) begin this many bytes below clu_sub, tile t's at
+  // clu_samp_tile_off(t) from there; 0: the segment has none, its split tiles sample the timestamp column
+  uint32_t clu_samp_back;
 };
 
 enum Agg : int { AGG_SUM = 0, AGG_MIN = 1, AGG_MAX = 2, AGG_COUNT = 3 };
@@ -256,6 +258,8 @@ struct QParams {
 constexpr uint32_t SPLIT_OK_NO_CLU_AGG = 2u;   // QParams::split_ok bit 1
 constexpr uint32_t SPLIT_OK_NO_CLU_SUB = 4u;   // bit 2 (env LK_NO_CLU_SUB, A/B and tests): scan_clu streams a split
                                                // tile's ranges whole instead of merging its whole sub-blocks' aggregates
+constexpr uint32_t SPLIT_OK_NO_CLU_SAMP = 8u;  // bit 3 (env LK_NO_CLU_SAMP, A/B and tests): scan_clu's boundary search
+                                               // samples the timestamp column instead of loading the tile's sample table
 // scan_lean's direct table: LDS words by late-column count NL (the hash table's 8 KB for NL >= 1, so the kernels keep
 // their occupancy), at most LEAN_DIR_MAXSPAN buckets
 constexpr uint32_t LEAN_DIR_WORDS0 = 1536;

@@ -174,7 +174,8 @@ class Engine:
 
     def __init__(self, device: int = 0, hbm_budget_bytes: int = 0, max_calls: int = 4, dict_compact_min_dead: int = 0,
                  load_threads: int = 0, formula_dense_max_cells: Optional[int] = None,
-                 formula_hash_slots: Optional[int] = None, cluster_values: Optional[bool] = None):
+                 formula_hash_slots: Optional[int] = None, cluster_values: Optional[bool] = None,
+                 cluster_samples: Optional[bool] = None):
         L = _lib.lib()
         h = ctypes.c_void_p()
         opts = {"device": device, "hbm_budget_bytes": int(hbm_budget_bytes), "max_calls": int(max_calls)}
@@ -188,6 +189,8 @@ class Engine:
             opts["formula_hash_slots"] = int(formula_hash_slots)
         if cluster_values is not None:            # False: segments load without the name-clustered value copy
             opts["cluster_values"] = bool(cluster_values)
+        if cluster_samples is not None:           # False: the copy's sub-block area without the timestamp sample tables
+            opts["cluster_samples"] = bool(cluster_samples)
         check(L.lk_engine_create(json.dumps(opts).encode(), ctypes.byref(h)))
         self._h = h
         self.device = device
